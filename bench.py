@@ -11,8 +11,14 @@ RCCL all-gather of the merged logits to every rank (N > 1).  Weak scaling.
 ``--gpus N`` without a launcher starts N ranks itself (sad/launch.py: a
 torch.distributed.run child); under a launcher the world size must equal N.
 
-Prints ONE JSON line on rank 0 (driver contract).  Besides the headline (bf16,
-configs[2]) it carries, measured in the same run on the same segments:
+Prints ONE JSON line on rank 0 (driver contract).  A plain run sets up, warms
+up, times ``--steps`` steps and prints the headline (bf16, configs[2]) with its
+``ms_per_step`` and the stage times its own events gave; ``--dump-outputs DIR``
+also writes what the last timed step computed (features, per-head logits,
+merged logits; the gathered logits with N > 1) as float32 ``DIR/<name>.npy`` --
+the PCM and the weights are seeded, so two builds can be compared array for
+array.  With ``--full`` the line also carries, measured in the same run on the
+same segments:
   * ``parity_mode``: the split-bf16 mode (dtype bf16x3) that meets the
     north-star |dlogit| <= 1e-3 -- its segments/s, roofline of its dominant
     kernel, max|dlogit| against the reference-generated golden logits and
@@ -225,10 +231,11 @@ class Mode:
     hand-off; libsad is built without those instructions (DESIGN.md 5c,
     tests/test_gpu_handoff.py, tests/test_isa_scan.py).
 
-    After the timed steps, ``run`` checks the LAST timed step's outputs: its
-    merged logits must equal an untimed sequential forward of the same PCM bit
-    for bit, and with N > 1 every rank's gathered logits must hold each rank's
-    merged rows (``timed_output_check``; a mismatch raises)."""
+    After the timed steps of a ``--full`` run, ``run`` checks the LAST timed
+    step's outputs: its merged logits must equal an untimed sequential forward
+    of the same PCM bit for bit, and with N > 1 every rank's gathered logits
+    must hold each rank's merged rows (``timed_output_check``; a mismatch
+    raises)."""
 
     def __init__(self, sd, dev, dtype, micro_batch, B, world, overlap=False):
         from sad.engine import Engine
@@ -305,7 +312,18 @@ class Mode:
             bb.append(e[1].elapsed_time(e[2]))
         return min(fe), min(bb)
 
-    def run(self, pcm, steps, warmup, profile=True):
+    def outputs(self):
+        """Copies of what the last step computed (the arrays of --dump-outputs)."""
+        out = {'features': self.feats, 'logits': self.logits, 'merged': self.merged}
+        if self.gathered is not None:
+            out['gathered'] = self.gathered
+        return {k: v.clone() for k, v in out.items()}
+
+    def run(self, pcm, steps, warmup, profile=True, check=True, keep_outputs=False):
+        """Warm up, time `steps` steps.  profile: bracket the dominant kernel's
+        launches of the last timed step; check: compare the last timed step with
+        a sequential forward and time the overlapped stages alone (both after
+        the timed region); keep_outputs: copy the last timed step's outputs."""
         from sad import _lib
         for _ in range(warmup):
             self.step(pcm)
@@ -343,8 +361,10 @@ class Mode:
             r['rank_gather_ms'] = [round(x[1].item(), 4) for x in allt]
         r['ms'] = r['elapsed'] * 1e3 / steps
         r['value'] = self.world * self.B * steps / r['elapsed']
-        r['timed_output_check'] = self.check_outputs(pcm)
-        if self.overlap:
+        if keep_outputs:
+            r['outputs'] = self.outputs()
+        r['timed_output_check'] = self.check_outputs(pcm) if check else None
+        if self.overlap and check:
             # the stage rooflines from the stages run alone; the in-step events
             # bracket the wait for the side stream's front end, not its work
             r['fe_ms_in_step'], r['bb_ms_in_step'] = r['fe_ms'], r['bb_ms']
@@ -417,6 +437,30 @@ def decisions(merged):
     return [ir.interpret_multihead_logits(row, 0.5, names)[0] for row in merged.cpu()]
 
 
+def headline(args, r, mode, world):
+    """The result line of a plain run (a --full run adds its legs to it): the
+    headline rate of the timed steps and what their own events gave."""
+    return {
+        'metric': '4s@32kHz segments/sec end-to-end (mel+ResNet+ensemble), 1/2/4/8 MI355X',
+        'value': round(r['value'], 1), 'unit': 'segments/s', 'n_gpus': world, 'steps': args.steps,
+        'warmup': args.warmup, 'ms_per_step': round(r['ms'], 3), 'higher_is_better': True, 'scaling': 'weak',
+        'vs_baseline': None, 'dtype': args.dtype,
+        'data': 'synthetic int16 PCM (counter-hash PRNG, generated in HBM) + random-init ResNet-18/6 heads '
+                '(hash PRNG, BN-calibrated; = the golden n6 fixture model)',
+        'config': {'workload': 'end-to-end inference: B int16 4 s segments resident in HBM -> mel front end '
+                               '-> ResNet-18@512x512 -> 6 binary heads -> merge (+RCCL all-gather of logits)',
+                   'segments_per_gpu_per_step': mode.B, 'heads': HEADS, 'distinct_backbones': 1,
+                   'micro_batch': mode.mb, 'parallelism': f'dp{world}',
+                   'frontend_overlapped': mode.overlap,
+                   'per_rank_ms_per_step': r['rank_ms_per_step'], 'per_rank_allgather_ms': r['rank_gather_ms']},
+        # HIP events on the main stream around each stage of the timed steps (means):
+        # front-end wait (overlapped: the side stream's maps), backbone, heads + merge, all-gather
+        'step_breakdown_ms': {'frontend_wait': round(r.get('fe_ms_in_step', r['fe_ms']), 3),
+                              'backbone': round(r.get('bb_ms_in_step', r['bb_ms']), 3),
+                              'heads_merge': round(r['heads_ms'], 3), 'allgather': round(r['gather_ms'], 4)},
+    }
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -427,6 +471,12 @@ def main():
     ap.add_argument('--micro-batch', type=int, default=0,
                     help='segments per backbone launch sequence (0: 2048 bf16, 512 bf16x3, 128 fp32); stem/layer1 '
                          'run in sub-batches of SAD_FRONT_MB (256 for bf16 with the fused layer1, else 32), layers 2-4 on the whole micro-batch')
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline also run and report the other legs: kernel brackets and stage '
+                         'rooflines, the timed-output check, accuracy, the bf16x3 parity and fp32 modes, the GEMM '
+                         'reference, ingestion and the CPU baseline (the options below that shape them need --full)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help="write the last timed step's outputs (rank 0) as float32 DIR/<name>.npy")
     ap.add_argument('--parity-steps', type=int, default=0, help='timed steps of the bf16x3 parity mode '
                                                                 '(0: max(steps // 3, 3); -1: skip)')
     ap.add_argument('--fp32-steps', type=int, default=2, help='timed steps of the fp32 mode (N = 1; 0: skip)')
@@ -434,10 +484,13 @@ def main():
                     help="1: each step's front end runs on a side stream during the previous step's backbone")
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--kernels-only', action='store_true',
-                    help='profiling runs: only the headline mode (no parity/fp32 legs, accuracy or CPU baseline)')
+                    help='profiling runs with --full: only the headline mode with its brackets and checks (no '
+                         'parity/fp32 legs, accuracy or CPU baseline)')
     ap.add_argument('--backend', default='nccl', choices=['nccl', 'gloo'], help='gloo: tests only')
     ap.add_argument('--one-device', action='store_true', help='every rank on cuda:0 (2-rank test on one GPU)')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be at least 1 and --warmup at least 0')
 
     if args.gpus > 1 and not launch.under_launcher():
         sys.exit(launch.relaunch(args.gpus, os.path.abspath(__file__), sys.argv[1:]))
@@ -462,9 +515,14 @@ def main():
 
     ov = bool(args.overlap_frontend)
     head = Mode(sd, dev, args.dtype, args.micro_batch or mbs[args.dtype], B, world, overlap=ov)
-    r = head.run(pcm, args.steps, args.warmup)
+    r = head.run(pcm, args.steps, args.warmup, profile=args.full, check=args.full,
+                 keep_outputs=bool(args.dump_outputs))
+    if args.dump_outputs and rank == 0:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, t in r.pop('outputs').items():
+            np.save(os.path.join(args.dump_outputs, name + '.npy'), t.to('cpu', torch.float32).numpy())
     p_steps = max(args.steps // 3, 3) if args.parity_steps == 0 else args.parity_steps
-    if args.kernels_only:
+    if args.kernels_only or not args.full:
         p_steps, args.fp32_steps, args.no_cpu_baseline = -1, 0, True
     par_mode, par = None, None
     if p_steps > 0:
@@ -474,7 +532,9 @@ def main():
             par_mode = Mode(sd, dev, 'bf16x3', mbs['bf16x3'], B, world, overlap=ov)
             par = par_mode.run(pcm, p_steps, 1)
 
-    if rank == 0:
+    if rank == 0 and not args.full:
+        print(json.dumps(headline(args, r, head, world)), flush=True)
+    elif rank == 0:
         from sad.engine import Engine
         # accuracy against the reference-generated fixtures (the bench model IS the golden n6 model) and
         # against the fp32 device path over this rank's whole batch
@@ -514,18 +574,7 @@ def main():
                         f'(FETCH_SIZE x2 + WRITE_SIZE, {traffic_src})')
         bb_alg = BACKBONE_FLOP * B / (r['bb_ms'] * 1e-3) / 1e12
         out = {
-            'metric': '4s@32kHz segments/sec end-to-end (mel+ResNet+ensemble), 1/2/4/8 MI355X',
-            'value': round(r['value'], 1), 'unit': 'segments/s', 'n_gpus': world, 'steps': args.steps,
-            'warmup': args.warmup, 'ms_per_step': round(r['ms'], 3), 'higher_is_better': True, 'scaling': 'weak',
-            'vs_baseline': None, 'dtype': args.dtype,
-            'data': 'synthetic int16 PCM (counter-hash PRNG, generated in HBM) + random-init ResNet-18/6 heads '
-                    '(hash PRNG, BN-calibrated; = the golden n6 fixture model)',
-            'config': {'workload': 'end-to-end inference: B int16 4 s segments resident in HBM -> mel front end '
-                                   '-> ResNet-18@512x512 -> 6 binary heads -> merge (+RCCL all-gather of logits)',
-                       'segments_per_gpu_per_step': B, 'heads': HEADS, 'distinct_backbones': 1,
-                       'micro_batch': head.mb, 'parallelism': f'dp{world}',
-                       'frontend_overlapped': ov,
-                       'per_rank_ms_per_step': r['rank_ms_per_step'], 'per_rank_allgather_ms': r['rank_gather_ms']},
+            **headline(args, r, head, world),
             'roofline': {'bound': 'mfma',
                          'kernel': DOMINANT[args.dtype][2],
                          'achieved': round(exe, 1), 'peak': peak, 'unit': 'TFLOP/s', 'frac': round(exe / peak, 4),
@@ -546,11 +595,6 @@ def main():
                                       'segments_per_s': round(B / (r['fe_ms'] * 1e-3), 1)}},
             'accuracy': accuracy(head),
             'timed_output_check': r['timed_output_check'],
-            # HIP events on the main stream around each stage of the timed steps (means):
-            # front-end wait (overlapped: the side stream's maps), backbone, heads + merge, all-gather
-            'step_breakdown_ms': {'frontend_wait': round(r.get('fe_ms_in_step', r['fe_ms']), 3),
-                                  'backbone': round(r.get('bb_ms_in_step', r['bb_ms']), 3),
-                                  'heads_merge': round(r['heads_ms'], 3), 'allgather': round(r['gather_ms'], 4)},
         }
         if par is not None:
             palg, pexe, pinfo = kernel_roofline(par, 3)

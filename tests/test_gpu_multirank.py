@@ -24,8 +24,8 @@ def _run(args, timeout=240):
 
 
 def test_bench_two_ranks_self_launched():
-    out = _run(['bench.py', '--gpus', '2', '--backend', 'gloo', '--one-device', '--batch', '64', '--steps', '2',
-                '--warmup', '1', '--parity-steps', '1', '--fp32-steps', '0', '--no-cpu-baseline'])
+    out = _run(['bench.py', '--full', '--gpus', '2', '--backend', 'gloo', '--one-device', '--batch', '64',
+                '--steps', '2', '--warmup', '1', '--parity-steps', '1', '--fp32-steps', '0', '--no-cpu-baseline'])
     lines = [json.loads(s) for s in out.splitlines() if s.startswith('{')]
     assert len(lines) == 1, out
     rec = lines[0]

@@ -11,7 +11,7 @@ for i in $(seq $N); do
     L=synthetic-audio-detection_amd/sad/libsad.so; [ "$lib" != tree ] && L=abl/libsad_$lib.so
     ev=""; args=""
     for t in ${envs//,/ }; do case "$t" in --*) args="$args $t";; *) ev="$ev $t";; esac; done
-    r=$(env SAD_LIB=$L $ev timeout -k 10 120 python bench.py --kernels-only --steps 20 $BENCH_ARGS $args | python3 -c 'import json,sys; d=json.loads(sys.stdin.read()); r=d["roofline"]; print(d["value"], r["launch_avg_us"], r["backbone"]["ms_per_step"], r.get("frontend", {}).get("ms_per_step"), (r.get("clock") or {}).get("sclk_mhz_median"))') || exit 1
+    r=$(env SAD_LIB=$L $ev timeout -k 10 120 python bench.py --full --kernels-only --steps 20 $BENCH_ARGS $args | python3 -c 'import json,sys; d=json.loads(sys.stdin.read()); r=d["roofline"]; print(d["value"], r["launch_avg_us"], r["backbone"]["ms_per_step"], r.get("frontend", {}).get("ms_per_step"), (r.get("clock") or {}).get("sclk_mhz_median"))') || exit 1
     echo "$cfg: $r"
   done
 done

@@ -3,4 +3,5 @@
 set -o pipefail
 mkdir -p gpurun_out
 timeout -k 10 1500 python -u -m pytest tests -m gpu -q -x --timeout 300 --timeout-method thread > gpurun_out/gputests.log 2>&1 || exit $?
-timeout -k 10 600 python bench.py > gpurun_out/bench.json 2> gpurun_out/bench.err
+BENCH_OUT=${BENCH_OUT:-bench_out}; mkdir -p "$BENCH_OUT"
+timeout -k 10 600 python bench.py --full > "$BENCH_OUT/bench.json" 2> "$BENCH_OUT/bench.err"

@@ -17,7 +17,7 @@ wave 0 of every workgroup and prints the in-kernel clock (median and per XCD),
 the launch span and the spread of workgroup end times.  For the clock under
 load, stamp every n-th launch inside the bench loop instead:
 
-    SAD_LIB=abl/libsad_stamps.so SAD_STAMP_EVERY=1000 python bench.py --kernels-only --steps 300"""
+    SAD_LIB=abl/libsad_stamps.so SAD_STAMP_EVERY=1000 python bench.py --full --kernels-only --steps 300"""
 import os
 import sys
 
