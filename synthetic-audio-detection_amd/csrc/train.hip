@@ -616,7 +616,8 @@ __global__ void col2im_kernel(const float* __restrict__ dcol, int H, int W, int 
 // ------------------------------------------------------------ optimizer --
 // torch.nn.utils.clip_grad_norm_(max_norm) (submodel_trainer.py:276) over one
 // flat fp32 gradient buffer: partial sums of squares, then
-// coef = min(max_norm / (||g|| + 1e-6), 1) and g *= coef.
+// coef = min(max_norm / (||g|| + 1e-6), 1) and g *= coef.  A NaN norm gives a
+// NaN coef, as torch.clamp(max=1.0) does (the reference guards only the loss).
 __global__ __launch_bounds__(256) void sqnorm_kernel(const float* __restrict__ g, int64_t n, double* __restrict__ part) {
   __shared__ double red[4];
   double s = 0.0;
@@ -643,7 +644,7 @@ __global__ __launch_bounds__(256) void clip_coef_kernel(const double* __restrict
   const float norm = (float)sqrt(s);
   const float coef = max_norm / (norm + 1e-6f);
   out[0] = norm;
-  out[1] = coef < 1.f ? coef : 1.f;
+  out[1] = coef > 1.f ? 1.f : coef;
 }
 
 __global__ void scale_kernel(float* __restrict__ g, int64_t n, const float* __restrict__ coef) {
@@ -848,7 +849,8 @@ static constexpr int kStatRowsMax = 512;  // >= the workgroup rows of any varian
 
 extern "C" int sad_conv_bn_train_workspace_size(int64_t N, int32_t H, int32_t W, int32_t Cout, int32_t k,
                                                 int32_t stride, int32_t pad, size_t* bytes) {
-  SAD_REQUIRE(bytes && N >= 0 && H > 0 && W > 0 && Cout > 0 && k > 0 && stride > 0 && pad >= 0, "bad args");
+  SAD_REQUIRE(bytes && N >= 0 && H > 0 && W > 0 && k > 0 && stride > 0 && pad >= 0, "bad args");
+  SAD_REQUIRE(Cout % 8 == 0 && Cout >= 8 && Cout <= 2048, "Cout must be a multiple of 8 in [8, 2048]");
   const int64_t P = N * ((H + 2 * pad - k) / stride + 1) * ((W + 2 * pad - k) / stride + 1);
   const size_t fused = (size_t)kStatRowsMax * 2 * Cout * sizeof(float) + 3 * (size_t)Cout * sizeof(float);
   const size_t unfused = (size_t)bn_nblocks(P, Cout) * 2 * Cout * sizeof(float) + 3 * (size_t)Cout * sizeof(float);
@@ -947,7 +949,8 @@ extern "C" int sad_conv_bn_train_run(const void* x, int64_t N, int32_t H, int32_
 }
 
 extern "C" int sad_bn_workspace_size(int64_t P, int32_t C, size_t* bytes) {
-  SAD_REQUIRE(bytes && C > 0, "bad args");
+  SAD_REQUIRE(bytes, "bad args");
+  SAD_REQUIRE(C % 8 == 0 && C >= 8 && C <= 2048, "C must be a multiple of 8 in [8, 2048]");
   *bytes = (size_t)bn_nblocks(P, C) * 2 * C * sizeof(float) + 3 * (size_t)C * sizeof(float);
   return SAD_OK;
 }
@@ -978,7 +981,8 @@ extern "C" int sad_bn_stats_run(const void* x, int64_t P, int32_t C, int32_t dty
 
 extern "C" int sad_bn_apply_run(const void* x, int64_t P, int32_t C, int32_t dtype, const float* stats,
                                 const void* res, const float* res_stats, int32_t relu, void* out, void* stream) {
-  SAD_REQUIRE(x && stats && out && P >= 0 && C % 8 == 0, "bad args");
+  SAD_REQUIRE(x && stats && out && P >= 0, "bad args");
+  SAD_REQUIRE(C % 8 == 0 && C >= 8 && C <= 2048, "C must be a multiple of 8 in [8, 2048]");
   const int64_t total = P * (C / 8);
   if (!total) return SAD_OK;
   if (dtype == SAD_BF16)
@@ -993,7 +997,8 @@ extern "C" int sad_bn_apply_run(const void* x, int64_t P, int32_t C, int32_t dty
 
 extern "C" int sad_bn_relu_maxpool_run(const void* x, int64_t n, int32_t H, int32_t W, int32_t C, int32_t dtype,
                                        const float* stats, void* out, void* stream) {
-  SAD_REQUIRE(x && stats && out && n >= 0 && H > 0 && W > 0 && C % 8 == 0, "bad args");
+  SAD_REQUIRE(x && stats && out && n >= 0 && H > 0 && W > 0, "bad args");
+  SAD_REQUIRE(C % 8 == 0 && C >= 8 && C <= 2048, "C must be a multiple of 8 in [8, 2048]");
   const int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
   const int64_t total = n * Ho * Wo * (C / 8);
   if (!total) return SAD_OK;
