@@ -170,6 +170,51 @@ int sad_resample_run(const sad_resample_plan* plan, const float* x, int64_t n_in
 int sad_window_absmax_run(const float* wav, int64_t n, int64_t window, int64_t hop, int64_t n_windows,
                           float* out, void* stream);
 
+/* --------------------------------------------------------- catalogue scan */
+/* Many files in one run (sad/scan.py, catalog_runner.py): the files' mono
+ * 32 kHz waveforms sit back to back in ONE fp32 arena; the device picks the
+ * windows to keep (slice_waveform, inference_runner.py:176-190) and, after the
+ * ensemble, does the per-file decisions of main (:292-349).  Both *_run calls
+ * are asynchronous, allocate nothing and use no float atomics: the same inputs
+ * give the same bytes on every run.
+ *
+ * Selection.  File f is wav[file_start[f], file_start[f] + file_len[f])
+ * (DEVICE int64 arrays; a file that does not lie inside [0, wav_len) has no
+ * candidates).  Its candidate windows start at range(0, file_len[f] - window + 1,
+ * hop); a candidate is kept unless max |x| < silence_threshold (fp32 compare;
+ * NaN propagates into the maximum as in sad_window_absmax_run, so it is kept).
+ *   offsets   [max_candidates] int64: the kept windows' ABSOLUTE arena offsets,
+ *             compacted in file order, then time order (an order-preserving
+ *             prefix scan), ready for sad_frontend_run_windows(wav, wav_len, ..);
+ *             entries past the kept count are not written;
+ *   row_start [n_files + 1] int64: file f's kept windows are rows
+ *             [row_start[f], row_start[f+1]) of offsets; row_start[n_files] is
+ *             the kept count.
+ * max_candidates bounds the candidates examined (the caller knows the file
+ * lengths; candidates past it are dropped).  ws: sad_scan_select_workspace_size. */
+int sad_scan_select_workspace_size(int64_t n_files, int64_t max_candidates, size_t* bytes);
+int sad_scan_select_run(const float* wav, int64_t wav_len, const int64_t* file_start, const int64_t* file_len,
+                        int64_t n_files, int64_t window, int64_t hop, float silence_threshold,
+                        int64_t max_candidates, int64_t* offsets, int64_t* row_start, void* ws, size_t ws_bytes,
+                        void* stream);
+/* Per-file post-processing of merged logits [B, C] fp32 (C = N + 1 <= 128, last
+ * column Real), file f owning rows [row_start[f], row_start[f+1]) (DEVICE int64
+ * [n_files + 1], as sad_scan_select_run writes it; clamped to [0, B]):
+ *   probs [B, C] fp32 = sigmoid(logits); with smooth != 0 each column is then
+ *         filtered along its file's rows as scipy gaussian_filter1d(sigma=2)
+ *         does (17 float64 taps, mode reflect, float64 accumulation rounded to
+ *         fp32; never across a file boundary) and each row is divided by its
+ *         fp32 sum when that is > 0;
+ *   label [B] int32: -1 = Real (p_real >= threshold and every synthetic p <
+ *         threshold), else the first argmax of the synthetic columns;
+ *   mean  [n_files, C] float64: column means of a file's final probs, summed in
+ *         a fixed order; zeros for a file without rows.
+ * ws: sad_scan_post_workspace_size bytes. */
+int sad_scan_post_workspace_size(int64_t B, int32_t C, int32_t smooth, size_t* bytes);
+int sad_scan_post_run(const float* logits, int64_t B, int32_t C, const int64_t* row_start, int64_t n_files,
+                      float threshold, int32_t smooth, float* probs, int32_t* label, double* mean, void* ws,
+                      size_t ws_bytes, void* stream);
+
 /* Replaces torchvision.transforms.Resize((512,512)) + repeat(3,1,1)
  * (inference_runner.py:172-174) for callers that want the image itself:
  * map [n, h, w] fp32 -> img [n, out_h, out_w] in `dtype` (one channel: the

@@ -74,6 +74,11 @@ SIGNATURES = {
     'sad_resample_out_len': (ctypes.c_int, [P, I64, ctypes.POINTER(I64)]),
     'sad_resample_run': (ctypes.c_int, [P, P, I64, P, I64, P]),
     'sad_window_absmax_run': (ctypes.c_int, [P, I64, I64, I64, I64, P, P]),
+    # catalogue scan (include/sad.h "catalogue scan")
+    'sad_scan_select_workspace_size': (ctypes.c_int, [I64, I64, ctypes.POINTER(SZ)]),
+    'sad_scan_select_run': (ctypes.c_int, [P, I64, P, P, I64, I64, I64, ctypes.c_float, I64, P, P, P, SZ, P]),
+    'sad_scan_post_workspace_size': (ctypes.c_int, [I64, I32, I32, ctypes.POINTER(SZ)]),
+    'sad_scan_post_run': (ctypes.c_int, [P, I64, I32, P, I64, ctypes.c_float, I32, P, P, P, P, SZ, P]),
     'sad_backbone_plan_create': (ctypes.c_int, [FPP, I32, I32, I32, I32, ctypes.POINTER(P)]),
     'sad_backbone_plan_destroy': (ctypes.c_int, [P]),
     'sad_backbone_workspace_size': (ctypes.c_int, [P, I64, ctypes.POINTER(SZ)]),
