@@ -93,7 +93,20 @@ typedef struct sad_frontend_cfg {
 typedef struct sad_frontend_plan sad_frontend_plan;
 
 /* The mel filterbank built on the host in float64 from cfg (htk triangles,
- * optional slaney area norm), rounded once to fp32. */
+ * optional slaney area norm), rounded once to fp32:
+ *   pts[i] = mel2hz(hz2mel(f_min) + (hz2mel(f_max) - hz2mel(f_min)) i / (n_mels + 1)), i <= n_mels + 1,
+ *   hz2mel(f) = 2595 log10(1 + f / 700); bin k sits at f = (sample_rate / 2) k / (n_fft / 2);
+ *   fb[k][m] = max(0, min((f - pts[m]) / (pts[m+1] - pts[m]), (pts[m+2] - f) / (pts[m+2] - pts[m+1]))),
+ *   times 2 / (pts[m+2] - pts[m]) with norm_slaney.
+ * Limits (SAD_ERR_ARG otherwise, checked on the host before any device call or
+ * allocation; *out is left untouched): n_fft = 2048, hop_length > 0,
+ * 0 < n_mels <= 1024, n_samples > n_fft / 2, and the bank's non-zero weights
+ * must lie within 792 consecutive FFT bins: bin_hi - bin_lo <= 791, bin_lo /
+ * bin_hi the lowest / highest bin with a non-zero weight in any filter (an
+ * all-zero filter counts as bin 0).  The kernels keep the power of bins
+ * bin_lo..bin_hi in an 800-float buffer per wave, 8 of them padding.  The
+ * reference's 20 Hz .. 12 kHz bank spans bins 2..768; a 0 Hz .. Nyquist bank
+ * (torchaudio's default f_max) spans 1..1023 and is refused. */
 int sad_frontend_plan_create(const sad_frontend_cfg* cfg, sad_frontend_plan** out);
 /* The same with the caller's filterbank: fbank = HOST fp32 [n_fft/2 + 1][n_mels]
  * (finite, >= 0; copied).  torchaudio builds its bank in fp32 arithmetic
@@ -101,7 +114,8 @@ int sad_frontend_plan_create(const sad_frontend_cfg* cfg, sad_frontend_plan** ou
  * the host layer passes that exact bank, so the device projects on the
  * reference's weights, not on a more accurate rounding of the same triangles
  * (which moves a mel bin next to a strong tone at a triangle's edge by up to
- * 6e-3 dB). */
+ * 6e-3 dB).  The same limits as sad_frontend_plan_create, the 791-bin span of
+ * the non-zero weights included. */
 int sad_frontend_plan_create_fb(const sad_frontend_cfg* cfg, const float* fbank, sad_frontend_plan** out);
 int sad_frontend_plan_destroy(sad_frontend_plan* plan);
 /* Number of STFT frames per segment (1 + n_samples / hop = 251). */
@@ -404,7 +418,12 @@ int sad_specaug_norm_run(const float* db, int64_t n, int32_t n_mels, int32_t n_f
 /* transforms.Resize((512,512)) (:200) then RandomResizedCrop's
  * resized_crop(i, j, h, w, (out_hw, out_hw)) (:466), one plane of the three
  * identical channels (:203).  boxes: device int32 [n,4] = {i, j, h, w} in the
- * 512x512 image, or NULL (= the val transform Resize((512,512)), :470). */
+ * 512x512 image, or NULL (= the val transform Resize((512,512)), :470).
+ * UPSAMPLING ONLY: both stages are the plain bilinear filter, which is what
+ * torchvision's antialiased resize reduces to when it enlarges.  So the map
+ * sides must be <= 512 and out_hw >= the box sides (the trainer: 128 x 251 maps,
+ * out_hw = 512); a downsampling call does NOT apply torchvision's antialias
+ * filter.  Boxes must lie inside the 512x512 image (not checked).  n <= 65535. */
 int sad_crop_resize_run(const float* map, int64_t n, int32_t h, int32_t w, const int32_t* boxes, int32_t out_hw,
                         int32_t dtype, void* img, void* stream);
 /* fp32 OIHW conv weight -> compute layout in dtype.  mode 0: [Cout][k][k][Cin]

@@ -47,6 +47,28 @@ __device__ __forceinline__ u16 f2bf(float f) {
 }
 __device__ __forceinline__ float bf2f(u16 h) { return __uint_as_float(((uint32_t)h) << 16); }
 
+// torchvision bilinear sample (align_corners=False, source index clamped at 0;
+// the antialias filter reduces to this for upsampling) of an `in`-long axis at
+// output pixel o of an `on`-long axis: (i0, i1, weight of i1).  resize_kernel
+// (frontend.hip) and crop_resize_kernel (train.hip) both go through bl_axis and
+// bl_lerp, whose fused operations are spelled out: left to the compiler, the two
+// kernels contracted the same expressions differently and Resize((512,512)) came
+// out an ulp apart between them (tests/test_gpu_image_prep.py).
+__device__ __forceinline__ void bl_axis(int o, int in, int on, int& i0, int& i1, float& l) {
+  const float sc = (float)in / on;
+  float f = __builtin_fmaf(sc, o + 0.5f, -0.5f);
+  f = f < 0.f ? 0.f : f;
+  i0 = min((int)floorf(f), in - 1);
+  i1 = min(i0 + 1, in - 1);
+  l = fminf(fmaxf(f - i0, 0.f), 1.f);
+}
+// (1 - ly) ((1 - lx) p00 + lx p01) + ly ((1 - lx) p10 + lx p11); exact for lx = ly = 0
+__device__ __forceinline__ float bl_lerp(float p00, float p01, float p10, float p11, float lx, float ly) {
+  const float ux = 1.f - lx, uy = 1.f - ly;
+  const float top = __builtin_fmaf(lx, p01, ux * p00), bot = __builtin_fmaf(lx, p11, ux * p10);
+  return __builtin_fmaf(ly, bot, uy * top);
+}
+
 // Bijective XCD-aware block remap (cdna_hip_programming.md 5, T1): consecutive
 // logical tiles land on the same XCD (blocks b, b+8, ... share one).
 __device__ __forceinline__ int xcd_remap(int bid, int nwg) {

@@ -135,6 +135,11 @@ __device__ __forceinline__ void wave_lds_sync() {
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
+// AmplitudeToDB(stype='power', amin 1e-10): 10 log10(max(p, 1e-10)).  A power at or
+// under the clamp (silence, an all-zero filter; NaN as fmaxf treated it) is exactly
+// -100 dB, the reference's value: the device log10f of 1e-10f is an ulp off -10.
+__device__ __forceinline__ float fe_db(float p) { return !(p > 1e-10f) ? -100.0f : 10.0f * log10f(p); }
+
 constexpr int FE_STAGE_MELS = 128;  // dB rows staged in LDS for coalesced stores
 constexpr int FE_POW = 800;         // power bins per wave in LDS (the reference's bank: 767)
 constexpr int FE_PWPAD = 8;         // zero slots before bin_lo (the mel windows' shifted starts)
@@ -522,18 +527,18 @@ __global__ __launch_bounds__(256, FM ? 3 : 2) void fe_mel_db_kernel(
       for (int i = 0; i < ml1; ++i) a1 = fmaf(pb[i], wb[i * 64], a1);
       if constexpr (FM) {  // frame-major: this frame's row of n_mels values
         float* row = out + (seg * n_frames + t) * n_mels;
-        if (mm[0] >= 0) row[mm[0]] = 10.0f * log10f(fmaxf(a0, 1e-10f));
-        if (mm[1] >= 0) row[mm[1]] = 10.0f * log10f(fmaxf(a1, 1e-10f));
+        if (mm[0] >= 0) row[mm[0]] = fe_db(a0);
+        if (mm[1] >= 0) row[mm[1]] = fe_db(a1);
       } else {
-        if (mm[0] >= 0) s_db[mm[0]][t - f_begin] = 10.0f * log10f(fmaxf(a0, 1e-10f));
-        if (mm[1] >= 0) s_db[mm[1]][t - f_begin] = 10.0f * log10f(fmaxf(a1, 1e-10f));
+        if (mm[0] >= 0) s_db[mm[0]][t - f_begin] = fe_db(a0);
+        if (mm[1] >= 0) s_db[mm[1]][t - f_begin] = fe_db(a1);
       }
     } else {
       for (int m = lane; m < n_mels; m += 64) {
         const int k0 = mel_start[m], len = mel_len[m], off = mel_off[m];
         float acc = 0.f;
         for (int q = 0; q < len; ++q) acc = fmaf(pw[k0 + q - bin_lo + FE_PWPAD], mel_w[off + q], acc);
-        out[(seg * n_mels + m) * n_frames + t] = 10.0f * log10f(fmaxf(acc, 1e-10f));
+        out[(seg * n_mels + m) * n_frames + t] = fe_db(acc);
       }
     }
     wave_lds_sync();  // pw / buf are rewritten by the next frame
@@ -782,7 +787,8 @@ __global__ __launch_bounds__(1024) void fe_normalize_fm_kernel(float* db_io, int
 }
 
 // Bilinear resize, align_corners=False (torchvision Resize on tensors; antialias
-// is a no-op for upsampling).  One thread per output pixel.
+// is a no-op for upsampling).  One thread per output pixel.  (bl_axis / bl_lerp,
+// common.hpp: shared with crop_resize_kernel, so both give the same bits.)
 template <typename OT>
 __global__ void resize_kernel(const float* __restrict__ in, int h, int w, int oh, int ow,
                               OT* __restrict__ out, int64_t total) {
@@ -791,17 +797,12 @@ __global__ void resize_kernel(const float* __restrict__ in, int h, int w, int oh
   const int ox = i % ow;
   const int oy = (i / ow) % oh;
   const int64_t n = i / ((int64_t)ow * oh);
-  const float sh = (float)h / oh, sw = (float)w / ow;
-  float fy = sh * (oy + 0.5f) - 0.5f;
-  fy = fy < 0.f ? 0.f : fy;
-  float fx = sw * (ox + 0.5f) - 0.5f;
-  fx = fx < 0.f ? 0.f : fx;
-  const int y0 = min((int)floorf(fy), h - 1), x0 = min((int)floorf(fx), w - 1);
-  const int y1 = min(y0 + 1, h - 1), x1 = min(x0 + 1, w - 1);
-  const float ly = fminf(fmaxf(fy - y0, 0.f), 1.f), lx = fminf(fmaxf(fx - x0, 0.f), 1.f);
+  int y0, y1, x0, x1;
+  float ly, lx;
+  bl_axis(oy, h, oh, y0, y1, ly);
+  bl_axis(ox, w, ow, x0, x1, lx);
   const float* p = in + n * h * w;
-  const float v = (1.f - ly) * ((1.f - lx) * p[y0 * w + x0] + lx * p[y0 * w + x1]) +
-                  ly * ((1.f - lx) * p[y1 * w + x0] + lx * p[y1 * w + x1]);
+  const float v = bl_lerp(p[y0 * w + x0], p[y0 * w + x1], p[y1 * w + x0], p[y1 * w + x1], lx, ly);
   if constexpr (sizeof(OT) == 2)
     out[i] = f2bf(v);
   else
@@ -857,10 +858,6 @@ static int frontend_plan_build(const sad_frontend_cfg* cfg, const float* fb_in, 
                                 : mel_fbank(n_freqs, cfg->f_min, cfg->f_max, cfg->n_mels, cfg->sample_rate,
                                             cfg->norm_slaney != 0);
   for (float v : fb) SAD_REQUIRE(v >= 0.f && v < 1e30f, "filterbank weights must be finite and >= 0");
-  auto* p = new sad_frontend_plan();
-  p->cfg = *cfg;
-  p->n_frames = 1 + cfg->n_samples / cfg->hop_length;
-  (void)hipGetDevice(&p->device);
   std::vector<int> st(cfg->n_mels), ln(cfg->n_mels), off(cfg->n_mels);
   std::vector<float> w;
   int lo = n_freqs, hi = -1;
@@ -882,6 +879,19 @@ static int frontend_plan_build(const sad_frontend_cfg* cfg, const float* fb_in, 
     lo = std::min(lo, a);
     hi = std::max(hi, b);
   }
+  // fe_mel_db writes bin k's power to slot k - lo + FE_PWPAD of its wave's
+  // FE_POW-float slice, on the lane path and in the CSR loop alike: a wider bank
+  // would write into the next wave's slice (0 Hz .. Nyquist covers bins 1..1023).
+  // Refused here, before any device call or allocation.
+  static_assert(FE_POW - FE_PWPAD - 1 == 791, "the limit documented in include/sad.h and DESIGN.md");
+  SAD_REQUIRE(hi - lo + FE_PWPAD < FE_POW,
+              "the mel filterbank's non-zero weights span FFT bins " + std::to_string(lo) + ".." + std::to_string(hi) +
+                  ": bin_hi - bin_lo = " + std::to_string(hi - lo) + " exceeds the limit of " +
+                  std::to_string(FE_POW - FE_PWPAD - 1) + " bins (lower f_max or raise f_min)");
+  auto* p = new sad_frontend_plan();
+  p->cfg = *cfg;
+  p->n_frames = 1 + cfg->n_samples / cfg->hop_length;
+  (void)hipGetDevice(&p->device);
   p->bin_lo = lo;
   p->bin_hi = hi;
   p->nnz = (int)w.size();
@@ -899,7 +909,7 @@ static int frontend_plan_build(const sad_frontend_cfg* cfg, const float* fb_in, 
   // sums bit-identical.
   std::vector<int> lane_tab(256, 0);
   std::vector<float> lane_w;
-  bool lanes_ok = cfg->n_mels <= FE_STAGE_MELS && hi - lo + FE_PWPAD < FE_POW;
+  bool lanes_ok = cfg->n_mels <= FE_STAGE_MELS;  // (the bin span fits the power buffer: checked above)
   if (lanes_ok) {
     std::vector<int> ord(cfg->n_mels);
     for (int m = 0; m < cfg->n_mels; ++m) ord[m] = m;

@@ -120,22 +120,11 @@ __global__ __launch_bounds__(1024) void specaug_norm_kernel(const float* __restr
   for (int i = threadIdx.x; i < count; i += blockDim.x) y[i] = (val(i) - mean_f) / denom;
 }
 
-// torchvision bilinear sample (align_corners=False, source index clamped at 0;
-// the antialias filter reduces to this for upsampling) of an ih x iw plane at
-// output pixel o of an `on`-long axis: (i0, i1, weight of i1).
-__device__ __forceinline__ void bl_axis(int o, int in, int on, int& i0, int& i1, float& l) {
-  const float sc = (float)in / on;
-  float f = sc * (o + 0.5f) - 0.5f;
-  f = f < 0.f ? 0.f : f;
-  i0 = min((int)floorf(f), in - 1);
-  i1 = min(i0 + 1, in - 1);
-  l = fminf(fmaxf(f - i0, 0.f), 1.f);
-}
-
 // Resize((512,512)) of the standardised map (submodel_trainer.py:200), then the
 // train transform RandomResizedCrop(512, scale=(0.8,1)) = resized_crop(i,j,h,w)
 // back to out x out (:466), composed exactly: each output pixel interpolates 4
-// crop pixels, each of which interpolates 4 map pixels.  The reference's 3
+// crop pixels, each of which interpolates 4 map pixels (bl_axis / bl_lerp,
+// common.hpp: the arithmetic of resize_kernel, bit for bit).  The reference's 3
 // identical channels (:203) are one plane here.
 // One workgroup per output row: the row's two crop rows (bi + cy0, bi + cy1)
 // are evaluated once over the box's columns into LDS (each 512-image pixel =
@@ -168,8 +157,7 @@ __global__ __launch_bounds__(256) void crop_resize_kernel(const float* __restric
     float a, b;
     bl_axis(iy, mh, R, y0, y1, a);
     bl_axis(ix, mw, R, x0, x1, b);
-    rows[r][cx] = (1.f - a) * ((1.f - b) * p[y0 * mw + x0] + b * p[y0 * mw + x1]) +
-                  a * ((1.f - b) * p[y1 * mw + x0] + b * p[y1 * mw + x1]);
+    rows[r][cx] = bl_lerp(p[y0 * mw + x0], p[y0 * mw + x1], p[y1 * mw + x0], p[y1 * mw + x1], b, a);
   }
   __syncthreads();
   OT* o = img + ((int64_t)n * out_hw + oy) * out_hw;
@@ -178,7 +166,7 @@ __global__ __launch_bounds__(256) void crop_resize_kernel(const float* __restric
     float lx;
     bl_axis(ox, bw, out_hw, cx0, cx1, lx);
     const float v00 = rows[0][cx0], v01 = rows[0][cx1], v10 = rows[1][cx0], v11 = rows[1][cx1];
-    st1(o + ox, (1.f - ly) * ((1.f - lx) * v00 + lx * v01) + ly * ((1.f - lx) * v10 + lx * v11));
+    st1(o + ox, bl_lerp(v00, v01, v10, v11, lx, ly));
   }
 }
 
