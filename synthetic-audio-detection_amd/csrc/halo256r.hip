@@ -26,6 +26,10 @@
 //  * so the only barrier is per chunk (every 9 K-steps): within a chunk the
 //    two waves of a SIMD drift freely and one's fragment reads overlap the
 //    other's MFMAs.
+//  * a chunk's 9 steps are unrolled (weight set, ky, kx and the step's piece
+//    are constants of the code) and carry no branch: the weights alternate
+//    between two register sets, a piece's lane constants come from a table
+//    built once per launch, and a piece the chunk lacks is masked, not skipped.
 // Per K-step and wave: 4 x 16-B weight loads, 32 ds_read_b128 (LDS ~50 % busy
 // at the MFMA rate), 64 MFMA 16x16x32.  Accumulators 128 VGPRs (2 x 16 tiles).
 // Epilogue: register-only (bias, ReLU, bf16, 8-B stores) or the fused average
@@ -50,7 +54,8 @@ constexpr int SCR = PW * TH;            // shortcut chunk: slots ty * 18 + tx
 constexpr int NDS = SCR / 8;            // 36 pieces per shortcut chunk
 constexpr int PATCH = NDP * 1024;
 constexpr int ROWB = PW * 128;
-constexpr int SMEM = 2 * PATCH;
+constexpr int NKT = (NDP + NW - 1) / NW + (NDS + NW - 1) / NW;  // table entries per wave: conv and shortcut pieces
+constexpr int SMEM = 2 * PATCH + NW * NKT * 256 + 1024;        // two patch buffers, the waves' piece tables, a dummy piece
 constexpr int BAD = 0x7FFFFFF0;
 constexpr uint64_t KEY = 0xd92dad912240ull;  // variant 30's column key {0,0,1,1,2,2,4,4,5,5,6,6,2,2,6,6,0,0}
 static_assert(SMEM <= 160 * 1024, "LDS budget");
@@ -112,8 +117,10 @@ __global__ __launch_bounds__(512, 1) void halo256r_kernel(BlockConvArgs a) {
       __builtin_amdgcn_make_buffer_rsrc((void*)a.in0, (short)0, (int)a.in0_bytes, 0x00020000);
   const __amdgpu_buffer_rsrc_t r1 =
       __builtin_amdgcn_make_buffer_rsrc((void*)(a.in1 ? a.in1 : a.in0), (short)0, (int)a.in1_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rw =
-      __builtin_amdgcn_make_buffer_rsrc((void*)a.wt, (short)0, (int)a.wt_bytes, 0x00020000);
+  // (ablations 1 / 4: no record of the weights in range -- every weight load
+  // returns zeros without traffic -- so the K loop carries no branch for them)
+  const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(
+      (void*)a.wt, (short)0, (a.ablate & 5) ? 0 : (int)a.wt_bytes, 0x00020000);
   const int ps0 = (int)a.in0_pstride * 2, ps1 = (int)a.in1_pstride * 2;
   const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
   const int lrow = lane >> 3;
@@ -121,7 +128,9 @@ __global__ __launch_bounds__(512, 1) void halo256r_kernel(BlockConvArgs a) {
                             // 4 no weight loads, 8 no epilogue, 128 no epilogue stores
 
   // ---- weights: lane (fr, fg) of fragment (i, h) = row cw + i*16 + fr, K bytes
-  // kb + h*64 + fg*16 of the step (kb = tap * cinb + chunk * 128)
+  // kb + h*64 + fg*16 of the step (kb = tap * cinb + chunk * 128); the wave-
+  // uniform part kb + i*16 rows rides in the load's SGPR offset, h*64 in its
+  // immediate: one lane offset serves the four loads
   const int wrow = a.wt_ld * 2;
   const int wlane = (cw + fr) * wrow + fg * 16;
   auto load_w = [&](int kb, h31_v4 (&wv)[TC][2]) __attribute__((always_inline)) {
@@ -129,71 +138,104 @@ __global__ __launch_bounds__(512, 1) void halo256r_kernel(BlockConvArgs a) {
     for (int i = 0; i < TC; ++i)
 #pragma unroll
       for (int h = 0; h < 2; ++h)
-        wv[i][h] = __builtin_amdgcn_raw_buffer_load_b128(rw, wlane + i * 16 * wrow + kb + h * 64, 0, 0);
+        wv[i][h] = __builtin_amdgcn_raw_buffer_load_b128(rw, wlane + h * 64,
+                                                         __builtin_amdgcn_readfirstlane(kb + i * 16 * wrow), 0);
   };
   auto kb_of = [&](int c, int tap) __attribute__((always_inline)) {
     return c < nc0 ? tap * cinb + c * 128 : 9 * cinb + (c - nc0) * 128;
   };
 
-  // ---- patch pieces of chunk c of tile t into buffer buf: piece q = wave + 8k
-  // (k = -1: all of this wave's pieces); the tile origin is wave-uniform and
-  // decoded once per chunk (TileO), not per piece
-  struct TileO {
-    int b, oy0, ox0;
-    bool ok;
+  // ---- patch pieces: piece q = wave + 8k of a chunk covers patch slots 8q ..
+  // 8q + 7, a lane's slot is s = 8q + lane / 8.  What a lane needs of slot s
+  // never changes during a launch, so it is tabled here, once (l1block.hip's
+  // DREL), for the wave's 6 conv pieces (k = 5: wave 0 only) and 5 shortcut
+  // pieces.  An entry: bits 4-29 the source offset relative to the tile's
+  // first patch pixel with the swizzled chunk position folded in (a multiple of
+  // 16); bits 0-3 the patch edges the slot lies on -- first / last patch row,
+  // first / last patch column: a slot on an edge that the tile shares with the
+  // image loads zeros; bit 30 always set; bit 31 a slot that no pixel has (past
+  // the patch; a shortcut chunk's columns 16 / 17).  A piece is bad (zeros, no
+  // traffic) where entry & mask is non-zero: the mask (NextP) is the tile's edge
+  // bits | bit 31, or all ones for a piece that the chunk does not have, which
+  // then goes to a dummy KB of LDS -- no branch, no division in a K-step.
+  // The table lies in LDS behind the patch buffers (256 B per wave and piece;
+  // held in 11 VGPRs it made the compiler spill): a step reads the entry of
+  // the next step's piece, so the read's latency hides behind the step.
+  constexpr int NKC = (NDP + NW - 1) / NW, NKS = (NDS + NW - 1) / NW;
+  static_assert(NKC + NKS == NKT, "table entries per wave");
+  int* const tab = (int*)(smem + 2 * PATCH) + wave * (NKT * 64) + lane;  // conv entry k at tab[64 k], shortcut at tab[64 (NKC + k)]
+#pragma unroll
+  for (int k = 0; k < NKC; ++k) {
+    const int s = 8 * (wave + NW * k) + lrow, py = s / PW, px = s - py * PW;
+    const int edge = (py == 0 ? 1 : 0) | (py == TH + 1 ? 2 : 0) | (px == 0 ? 4 : 0) | (px == TW + 1 ? 8 : 0);
+    const int off = (py * a.W + px) * ps0 + (((lane & 7) ^ h31_key(px)) << 4);
+    tab[64 * k] = s < PR ? (off & 0x3FFFFFF0) | edge | (1 << 30) : (int)0xC0000000;
+  }
+#pragma unroll
+  for (int k = 0; k < NKS; ++k) {
+    const int s = 8 * (wave + NW * k) + lrow, ty = s / PW, tx = s - ty * PW;
+    const int off = (ty * a.W1 + tx) * (a.ss1 * ps1) + (((lane & 7) ^ h31_key(tx)) << 4);
+    tab[64 * (NKC + k)] = tx < TW ? (off & 0x3FFFFFF0) | (1 << 30) : (int)0xC0000000;
+  }
+  // the wave-uniform part of a chunk's pieces (chunk c of tile t), decoded once
+  // per chunk: source, base offset, mask, piece count (0 past the workgroup's
+  // last tile, and in the loop under the ablations 1 / 2), table offset
+  struct NextP {
+    __amdgpu_buffer_rsrc_t r;
+    int base, mask, lim, tk;
   };
-  auto tile_o = [&](int t) __attribute__((always_inline)) {
+  auto next_p = [&](int t, int c, int abm) __attribute__((always_inline)) {
     const int tt = __builtin_amdgcn_readfirstlane(t);
     const int b = tt / tiles_img, rem = tt - b * tiles_img;
     const int ty = rem / tiles_x;
-    return TileO{b, ty * TH, (rem - ty * tiles_x) * TW, tt < tp_end};
+    const int oy0 = ty * TH, ox0 = (rem - ty * tiles_x) * TW;
+    const bool sc = c >= nc0;
+    const int base = sc ? ((b * a.H1 + oy0 * a.ss1) * a.W1 + ox0 * a.ss1) * ps1 + (c - nc0) * 128
+                        : ((b * a.H + oy0 - 1) * a.W + ox0 - 1) * ps0 + c * 128;
+    const int mask = (int)0x80000000 | (sc ? 0
+                                           : (oy0 == 0 ? 1 : 0) | (oy0 + TH == a.H ? 2 : 0) | (ox0 == 0 ? 4 : 0) |
+                                                 (ox0 + TW == a.W ? 8 : 0));
+    return NextP{sc ? r1 : r0, base, mask, tt < tp_end && !(ab & abm) ? (sc ? NDS : NDP) : 0, sc ? 64 * NKC : 0};
   };
-  auto issue_patch = [&](const TileO& to, int c, int buf, int k_only) __attribute__((always_inline)) {
-    if (!to.ok) return;
-    const int b = to.b, oy0 = to.oy0, ox0 = to.ox0;
-    int lr;  // opaque lane row: keeps the per-piece (py, px) from being hoisted into registers
-    asm volatile("v_mov_b32 %0, %1" : "=v"(lr) : "v"(lrow));
-    const unsigned dst = lds0 + buf * PATCH;
-    if (c < nc0) {
-      const int base = ((b * a.H + oy0 - 1) * a.W + ox0 - 1) * ps0 + c * 128;
+  // the table entry of piece k of the chunk np describes (a shortcut chunk has
+  // no k = 5: the read then lands on the next wave's table or the dummy piece,
+  // inside the allocation, and the piece is masked whatever it returns)
+  auto entry = [&](const NextP& np, int k) __attribute__((always_inline)) { return tab[np.tk + 64 * k]; };
+  // piece k of this wave into the buffer at LDS offset boff (e: its table entry)
+  auto piece = [&](const NextP& np, int boff, int k, int e) __attribute__((always_inline)) {
+    const int q = wave + NW * k;
+    const bool has = q < np.lim;  // uniform
+    const int m = has ? np.mask : -1;
+    dma16_m0(np.r, (e & m) ? BAD : np.base + (e & 0x3FFFFFF0), lds0 + (has ? boff + q * 1024 : SMEM - 1024));
+  };
+  auto pieces = [&](const NextP& np, int boff) __attribute__((always_inline)) {
 #pragma unroll
-      for (int k = 0; k < (NDP + NW - 1) / NW; ++k) {
-        const int q = wave + NW * k;
-        if ((k_only < 0 || k == k_only) && q < NDP) {
-          const int s = 8 * q + lr, py = s / PW, px = s - py * PW;
-          const int iy = oy0 - 1 + py, ix = ox0 - 1 + px;
-          const int off = (s < PR && (unsigned)iy < (unsigned)a.H && (unsigned)ix < (unsigned)a.W)
-                              ? base + (py * a.W + px) * ps0 + (((lane & 7) ^ h31_key(px)) << 4)
-                              : BAD;
-          dma16_m0(r0, off, dst + q * 1024);
-        }
-      }
-    } else {
-      const int base = ((b * a.H1 + oy0 * a.ss1) * a.W1 + ox0 * a.ss1) * ps1 + (c - nc0) * 128;
-#pragma unroll
-      for (int k = 0; k < (NDS + NW - 1) / NW; ++k) {
-        const int q = wave + NW * k;
-        if ((k_only < 0 || k == k_only) && q < NDS) {
-          const int s = 8 * q + lr, ty = s / PW, tx = s - ty * PW;
-          const int off = tx < TW ? base + (ty * a.W1 + tx) * (a.ss1 * ps1) + (((lane & 7) ^ h31_key(tx)) << 4)
-                                  : BAD;
-          dma16_m0(r1, off, dst + q * 1024);
-        }
-      }
-    }
+    for (int k = 0; k < NKC; ++k) piece(np, boff, k, entry(np, k));
   };
 
   // ---- prologue loads: the first chunk's patch, step 0's weights, the bias of
   // this lane's channels (every tile's accumulators start at the bias: the
   // epilogue adds nothing)
-  issue_patch(tile_o(tp_begin), 0, 0, -1);
+  pieces(next_p(tp_begin, 0, 0), 0);
   f32x4 biasv[TC];
 #pragma unroll
   for (int i = 0; i < TC; ++i) biasv[i] = *(const f32x4*)(a.bias + cw + i * 16 + fg * 4);
-  // wnxt: the weights in flight (loaded one step ahead); wcur: this step's,
-  // copied from wnxt only after the step's wait
-  h31_v4 wcur[TC][2], wnxt[TC][2];
-  load_w(0, wnxt);
+  // two weight sets used in turn: step s of a chunk multiplies from set s & 1
+  // while set (s + 1) & 1 is loaded for the next one -- no copies between the
+  // steps of a chunk.  A chunk has an odd number of steps (9, a shortcut chunk
+  // 1), so its last step leaves the next chunk's first weights in set 1: they
+  // move to set 0 once per chunk, behind the chunk's wait.  (One chunk body per
+  // set parity instead costs no move, but the compiler then no longer keeps the
+  // accumulators and the sets in place across the bodies: 200-580 VGPRs
+  // spilled in every instantiation.)  The loads are compiler-tracked buffer
+  // loads, so the compiler waits for a set before the step's first MFMA; the
+  // patch DMA pieces (inline asm) are not tracked, and being older than the
+  // loads that follow them, each such wait also covers the pieces issued before
+  // it -- conservative, never short.  An inline-asm load with a hand-counted
+  // vmcnt gave wrong results: the register allocator may copy an asm output
+  // before the data has landed.
+  h31_v4 wset[2][TC][2];
+  load_w(0, wset[1]);
 
   f32x4 acc[TC][TP];
 #pragma unroll
@@ -201,43 +243,40 @@ __global__ __launch_bounds__(512, 1) void halo256r_kernel(BlockConvArgs a) {
 #pragma unroll
     for (int j = 0; j < TP; ++j) acc[i][j] = biasv[i];
 
-  // this step's weights: the copy from wnxt is where the compiler waits for
-  // the loads (weights are compiler-tracked buffer loads; the patch DMA pieces,
-  // inline asm, are not tracked, so each such wait also covers the pieces
-  // issued before it -- conservative, never short).  An inline-asm load with a
-  // hand-counted vmcnt gave wrong results: the register allocator may copy an
-  // asm output before the data has landed.
-  auto take_w = [&]() __attribute__((always_inline)) {
+  // the lane's fragment offsets for tap column kx and K-half h: patch column
+  // kx + fr, chunk (4 h + fg) at its key position, plus this wave's first row;
+  // a step adds the buffer's offset and immediates (ky, the fragment's row)
+  int fb[3][2];
 #pragma unroll
-    for (int i = 0; i < TC; ++i)
+  for (int kx = 0; kx < 3; ++kx)
 #pragma unroll
-      for (int h = 0; h < 2; ++h) wcur[i][h] = wnxt[i][h];
-  };
+    for (int h = 0; h < 2; ++h)
+      fb[kx][h] = r0w * ROWB + (kx + fr) * 128 + (((4 * h + fg) ^ h31_key(kx + fr)) << 4);
 
-  // ---- one K-step: 64 MFMAs; the pixel fragment of output row j, half h is at
-  // patch row j + ky, column kx + fr (shortcut chunks: ky = kx = 0)
-  auto step = [&](int pbuf, int ky, int kx) __attribute__((always_inline)) {
-    const int pbase = pbuf * PATCH + (ky + r0w) * ROWB;
-    const int o0 = (kx + fr) * 128 + ((fg ^ h31_key(kx + fr)) << 4);
-    const int o1 = (kx + fr) * 128 + (((fg + 4) ^ h31_key(kx + fr)) << 4);
-    const char* pb0 = smem + pbase + o0;
-    const char* pb1 = smem + pbase + o1;
+  // ---- one K-step: 64 MFMAs from weight set wv; the pixel fragment of output
+  // row j, half h is at patch row j + KY, column KX + fr of the buffer at LDS
+  // offset boff (shortcut chunks: KY = KX = 0)
+  auto step = [&](int boff, auto kyc, auto kxc, const h31_v4 (&wv)[TC][2]) __attribute__((always_inline)) {
+    constexpr int KY = decltype(kyc)::value, KX = decltype(kxc)::value;
     auto half = [&](auto hc) __attribute__((always_inline)) {
       constexpr int h = decltype(hc)::value;
       // bf16: W_h.X_h.  Split-bf16, half 0 (the hi fragment): W_hi.X_hi and
       // W_lo.X_hi; half 1 (the lo fragment): W_hi.X_lo.
       constexpr int NM = X3 && h == 0 ? 2 : 1;  // weight halves per fragment
-      const char* pb = h ? pb1 : pb0;
+      // one add per half, opaque, or the compiler keeps the sums in registers
+      unsigned po;
+      asm volatile("v_add_u32 %0, %1, %2" : "=v"(po) : "s"(lds0 + boff), "v"(fb[KX][h]));
+      const auto* pb = (const __attribute__((address_space(3))) char*)(uintptr_t)po + KY * ROWB;
       uint4 bf[TP];
 #pragma unroll
-      for (int j = 0; j < TP; ++j) bf[j] = *(const uint4*)(pb + j * ROWB);
+      for (int j = 0; j < TP; ++j) bf[j] = __builtin_bit_cast(uint4, *(const __attribute__((address_space(3))) h31_v4*)(pb + j * ROWB));
 #pragma unroll
       for (int j = 0; j < TP; ++j)
 #pragma unroll
         for (int m = 0; m < NM; ++m)
 #pragma unroll
           for (int i = 0; i < TC; ++i)
-            mfma_chunk<u16>(__builtin_bit_cast(uint4, wcur[i][X3 ? m : h]), bf[j], acc[i][j]);
+            mfma_chunk<u16>(__builtin_bit_cast(uint4, wv[i][X3 ? m : h]), bf[j], acc[i][j]);
       // reads run 4 fragments ahead of the MFMAs that consume them
       __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);
 #pragma unroll
@@ -252,6 +291,9 @@ __global__ __launch_bounds__(512, 1) void halo256r_kernel(BlockConvArgs a) {
   };
 
   auto epilogue = [&](int t) __attribute__((always_inline)) {
+    int el;  // opaque lane id: the store addresses' lane parts are not kept in registers across the K loop
+    asm volatile("v_mov_b32 %0, %1" : "=v"(el) : "v"(lane));
+    const int fr = el & 15, fg = el >> 4;
     const int b = t / tiles_img, rem = t - b * tiles_img;
     const int oy0 = (rem / tiles_x) * TH, ox0 = (rem - (rem / tiles_x) * tiles_x) * TW;
     if constexpr (POOL) {
@@ -340,49 +382,53 @@ __global__ __launch_bounds__(512, 1) void halo256r_kernel(BlockConvArgs a) {
       for (int j = 0; j < TP; ++j) acc[i][j] = biasv[i];
   };
 
-  // ---- the K loop: tiles -> chunks -> steps.  Per step: wait for its weights;
-  // at a chunk start also the barrier that publishes the chunk's patch (and
-  // frees the other buffer); then this step's patch piece for the next chunk
-  // (conv taps 1..6: one piece per wave; a shortcut chunk: all of them), the
-  // next step's weights, and the MFMAs.
-  int u = 0;  // chunk counter (patch buffer parity)
+  // ---- the K loop: tiles -> chunks -> steps, the steps of a chunk unrolled:
+  // weight set, ky, kx and the step's piece are constants of the code.  Per
+  // chunk: the wait and the barrier that publish its patch (and free the other
+  // buffer), the weight set's move.  Per step: the next step's weights into the
+  // other set (after the chunk's last step the next chunk's first; after a
+  // tile's last a harmless reload of step 0's, so the wait counts stay
+  // uniform), this step's patch piece for the next chunk (conv taps 1..6: one
+  // piece per wave; a shortcut chunk: all of them), and the MFMAs.  A shortcut
+  // chunk is the conv chunk's step 0 (ky = kx = 0) and leaves after it.
+  int pbuf = 0;  // chunk counter & 1: the chunk's patch buffer
   bool post_epi = false;
   for (int t = tp_begin; t < tp_end; ++t) {
     for (int c = 0; c < nch; ++c) {
       const bool sc = c >= nc0;
-      const int nsteps = sc ? 1 : 9;
       const int nt = c + 1 < nch ? t : t + 1, ncn = c + 1 < nch ? c + 1 : 0;  // next chunk
-      const TileO nto = tile_o(nt);
-      const int pbuf = u & 1;
-      for (int tap = 0; tap < nsteps; ++tap) {
-        if (tap == 0) {
-          // the chunk's patch pieces (this wave's); after a tile's epilogue its
-          // stores (the youngest operations) may stay in flight
-          if (post_epi)
-            asm volatile("s_waitcnt vmcnt(%0)" ::"n"(POOL ? 0 : (X3 ? 2 : 1) * TC * TP / 2) : "memory");
-          else
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-          post_epi = false;
-          __builtin_amdgcn_s_barrier();
-          asm volatile("" ::: "memory");  // LDS changed behind the barrier
-        }
-        take_w();
-        if (!(ab & 1)) {
-          // the next step's weights (after the last step: a harmless reload of
-          // step 0's, so the wait counts stay uniform)
-          const int kbn = tap + 1 < nsteps ? kb_of(c, tap + 1) : kb_of(ncn, 0);
-          if (!(ab & 4)) load_w(kbn, wnxt);
-          if (ab & 2) {
-          } else if (sc) {
-            issue_patch(nto, ncn, pbuf ^ 1, -1);  // waited for at the next step (a chunk start)
-          } else if (tap >= 1 && tap <= 6) {
-            issue_patch(nto, ncn, pbuf ^ 1, tap - 1);
-          }
-        }
-        const int ky = sc ? 0 : tap / 3, kx = sc ? 0 : tap - 3 * (tap / 3);
-        step(pbuf, ky, kx);
-      }
-      ++u;
+      const NextP np = next_p(nt, ncn, 3);
+      const int kbn0 = kb_of(ncn, 0);
+      const int boff = pbuf * PATCH, nboff = PATCH - boff;
+      // the chunk's patch pieces (this wave's); after a tile's epilogue its
+      // stores (the youngest operations) may stay in flight
+      if (post_epi)
+        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(POOL ? 0 : (X3 ? 2 : 1) * TC * TP / 2) : "memory");
+      else
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      post_epi = false;
+      __builtin_amdgcn_s_barrier();
+      asm volatile("" ::: "memory");  // LDS changed behind the barrier
+#pragma unroll
+      for (int i = 0; i < TC; ++i)
+#pragma unroll
+        for (int h = 0; h < 2; ++h) wset[0][i][h] = wset[1][i][h];
+      load_w(sc ? kbn0 : cinb + c * 128, wset[1]);
+      if (sc) pieces(np, nboff);  // waited for at the next step (a chunk start)
+      int trel = entry(np, 0);  // the table entry of the next step's piece
+      __builtin_amdgcn_sched_barrier(0);
+      step(boff, std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{}, wset[0]);
+      if (!sc)
+        l1b_for<8>([&](auto tc1) __attribute__((always_inline)) {
+          constexpr int tap = decltype(tc1)::value + 1;
+          __builtin_amdgcn_sched_barrier(0);  // nothing moves between steps
+          load_w(tap < 8 ? (tap + 1) * cinb + c * 128 : kbn0, wset[(tap + 1) & 1]);
+          if constexpr (tap <= NKC) piece(np, nboff, tap - 1, trel);
+          if constexpr (tap < NKC) trel = entry(np, tap);
+          __builtin_amdgcn_sched_barrier(0);
+          step(boff, std::integral_constant<int, tap / 3>{}, std::integral_constant<int, tap % 3>{}, wset[tap & 1]);
+        });
+      pbuf ^= 1;
     }
     if (!(ab & 8)) epilogue(t);
     post_epi = true;
@@ -423,6 +469,9 @@ int launch_halo256r(const BlockConvArgs& a, hipStream_t s, bool x3) {
               "variant 31: pixel strides");
   SAD_REQUIRE(a.out || a.pool_out, "null output");
   SAD_REQUIRE(a.M == (int64_t)a.N * a.H * a.W, "variant 31: M = N H W");
+  SAD_REQUIRE((int64_t)(18 * a.W + 18) * a.in0_pstride * 2 < (1 << 30) &&
+                  (!a.in1 || (int64_t)(16 * a.W1 + 16) * a.ss1 * a.in1_pstride * 2 < (1 << 30)),
+              "variant 31: a patch's source offsets must fit the piece table's 30 bits");
   if (a.pool_out) {
     SAD_REQUIRE(a.H == 16 && a.W == 16 && a.Cout % 256 == 0,
                 "variant 31 fused average pool: a 16 x 16 tile must be one image, Cout % 256");
