@@ -741,8 +741,8 @@ bool halo256rs2_ok(const BlockConvArgs& a);
 // halo kernel (variant 20): bf16 stride-1 3x3 with Cout <= 128 (layer1, layer2's
 // second block), where the implicit GEMM is L2->LDS-fill bound (convbench,
 // mb 128: layer1 c2 261 vs 350 us, layer2 c1 187 vs 218 us); for Cout >= 256
-// the patch would be re-loaded per 64-channel tile.  It is also the only
-// kernel taking `res`.
+// the patch would be re-loaded per 64-channel tile.  It also takes `res`
+// for any Cout (variants 13, 31 and 41 take it for theirs).
 // (split-bf16: logical channels; the kernel sees 2 Cin bf16 channels)
 static bool halo_ok(const BlockConvArgs& a, int dtype) {
   return (dtype == SAD_BF16 || dtype == SAD_BF16X3) && a.KH == 3 && a.KW == 3 && a.stride == 1 && a.pad == 1 &&
@@ -766,11 +766,13 @@ bool layer2_v31() {
   return v;
 }
 // variant 31's contract (either tile width): 3x3/s1/p1, 16 x 16 tiles, whole
-// 128-B chunks, no epilogue residual / statistics
-static bool halo31_ok(const BlockConvArgs& a) {
+// 128-B chunks, no statistics; an epilogue residual in bf16 only, and then no
+// shortcut source beside it
+static bool halo31_ok(const BlockConvArgs& a, int dtype) {
   return a.KH == 3 && a.KW == 3 && a.stride == 1 && a.pad == 1 && a.Cout % 128 == 0 && a.H % 16 == 0 &&
-         a.W % 16 == 0 && a.Ho == a.H && a.Wo == a.W && !a.res && !a.st_part && a.Cin % 64 == 0 &&
-         (!a.in1 || a.Cin1 % 64 == 0) && (!a.pool_out || (a.H == 16 && a.W == 16 && a.Cout % 256 == 0));
+         a.W % 16 == 0 && a.Ho == a.H && a.Wo == a.W && (!a.res || (dtype == SAD_BF16 && !a.in1)) && !a.st_part &&
+         a.Cin % 64 == 0 && (!a.in1 || a.Cin1 % 64 == 0) &&
+         (!a.pool_out || (a.H == 16 && a.W == 16 && a.Cout % 256 == 0));
 }
 // SAD_X3_L2_V31 (split-bf16): layer2's stride-1 convs (layer2.0's conv2 +
 // downsample, layer2.1's two; identity / downsample as shortcut columns) on
@@ -931,6 +933,13 @@ static int halo256_mode() {
   }();
   return v;
 }
+// bf16 identity blocks of layer3/4 (Cout a multiple of 256, 16 x 16 tiles):
+// the shortcut goes to variant 31 as an epilogue residual, as layer1/2's goes
+// to their kernels, when variant 31 runs these convs at all (SAD_HALO256 = 2,
+// the default; 0 / 1 keep the identity as K columns on variants 13 / 30)
+bool v31_identity_residual(int dtype, int cout, int Ho) {
+  return dtype == SAD_BF16 && halo256_mode() == 2 && cout % 256 == 0 && Ho % 16 == 0;
+}
 static int block_device_cus() {
   static int cus[64] = {};
   int dev = 0;
@@ -949,11 +958,11 @@ int default_block_variant(const BlockConvArgs& a, int dtype) {
     // layer1 (64 -> 64): the resident-weight split-bf16 kernel (half the channels per workgroup)
     if (halo_ok(a, dtype) && a.Cin == 64 && a.Cout == 64 && x3_l1_variant() == 42) return 42;
     if (halo_ok(a, dtype) && a.Cin == 64 && a.Cout == 64 && x3_rw()) return 26;
-    if (x3_layer2_v31() && a.Cout == 128 && halo31_ok(a)) return 31;
+    if (x3_layer2_v31() && a.Cout == 128 && halo31_ok(a, dtype)) return 31;
     // layer3/4 stride-1 convs: variant 30's split form (or 31's; chosen
     // whatever the grid size: their K orders differ from variant 13's)
     if (halo256_mode() != 0 && (halo256_mode() == 1 || x3_halo256_variant() == 30) && halo256_ok(a)) return 30;
-    if (halo256_mode() == 2 && x3_halo256_variant() == 31 && a.Cout % 256 == 0 && halo31_ok(a)) return 31;
+    if (halo256_mode() == 2 && x3_halo256_variant() == 31 && a.Cout % 256 == 0 && halo31_ok(a, dtype)) return 31;
     // the stride-2 convs (layer2/3/4's conv1): variant 44's split form (chosen
     // whatever the grid size: its K order differs from the implicit GEMM's)
     if (x3_s2_variant() == 44 && halo256rs2_ok(a) && a.Cout % 256 == 0) return 44;
@@ -968,7 +977,11 @@ int default_block_variant(const BlockConvArgs& a, int dtype) {
   if (dtype == SAD_BF16 && l2_ds_rw() && l2conv_ds_ok(a)) return 41;
   // layer2's 128-channel stride-1 convs (incl. conv2 + downsample / identity as
   // shortcut columns): variant 31 with 128-channel tiles
-  if (dtype == SAD_BF16 && layer2_v31() && a.Cout == 128 && halo31_ok(a)) return 31;
+  if (dtype == SAD_BF16 && layer2_v31() && a.Cout == 128 && !a.res && halo31_ok(a, dtype)) return 31;
+  // layer3/4's identity blocks (run_blocks, resnet.hip's identity_epilogue):
+  // variant 31 with the shortcut as an epilogue residual -- before the halo
+  // kernel's line below, and whatever the batch size (see the layer3/4 choice)
+  if (dtype == SAD_BF16 && halo256_mode() == 2 && a.res && a.Cout % 256 == 0 && halo31_ok(a, dtype)) return 31;
   if (halo_ok(a, dtype) && (a.res || (a.Cout <= 128 && layer2_halo())))
     return a.Cout == 128 && !a.res && halo_c128_variant() == 22 ? 22 : 20;
   // layer3/4 stride-1 convs: the patch-resident kernels (bf16 only: the fp32
@@ -1007,7 +1020,7 @@ static int pool_tile(int v) {
 bool block_conv_can_pool(const BlockConvArgs& a, int dtype) {
   const int v = default_block_variant(a, dtype);
   const int bp = pool_tile(v);
-  return bp > 0 && a.Ho * a.Wo == bp && !a.res && a.M % bp == 0 && (v != 31 || a.Cout % 256 == 0);
+  return bp > 0 && a.Ho * a.Wo == bp && (!a.res || v == 31) && a.M % bp == 0 && (v != 31 || a.Cout % 256 == 0);
 }
 static bool variant_fits(int v, int cout) {
   if (v == 26 || v == 42) return cout == 64;
@@ -1181,8 +1194,9 @@ int launch_block_conv(const BlockConvArgs& a_in, int dtype, hipStream_t s, int v
 #endif
   }
   if (v == 31) {
-    SAD_REQUIRE((dtype == SAD_BF16 || dtype == SAD_BF16X3) && halo31_ok(a_in),
-                "variant 31: bf16 / split-bf16 3x3/s1/p1, Cout % 128, 16 x 16 tiles");
+    SAD_REQUIRE((dtype == SAD_BF16 || dtype == SAD_BF16X3) && halo31_ok(a_in, dtype),
+                "variant 31: bf16 / split-bf16 3x3/s1/p1, Cout % 128, 16 x 16 tiles; epilogue residual in bf16 only, "
+                "without a shortcut source");
     return launch_halo256r(a, s, dtype == SAD_BF16X3);
   }
   if (v == 32) {

@@ -5,7 +5,9 @@
 // [-> + shortcut] -> relu, inference_runner.py:49-51 via timm resnet18
 // forward_features) for the layer3 / layer4 convs with stride 1:
 //   out[px, co] = act( sum_{tap, ci} X0[px + tap; ci] W0[co, tap, ci]
-//                    + sum_{k1} X1[px * ss1; k1] W1[co, k1] + bias[co] )
+//                    + sum_{k1} X1[px * ss1; k1] W1[co, k1] + bias[co] + R[px, co] )
+// (X1: the downsample shortcut's source as K columns; R: the identity shortcut
+// as an epilogue residual, bf16 only; the split-bf16 form takes both as X1)
 //
 // Why a third form.  Variants 13 and 30 stage BOTH operands in LDS and so need
 // a workgroup barrier per 64-deep K-step (the weight stage of step g+1 is
@@ -86,11 +88,16 @@ __device__ __forceinline__ uint32_t h31_relu2(uint32_t x) {
 // both weight halves on the hi fragment) + W_hi.X_lo (half 1): 96 MFMAs per
 // K-step and wave on the same operand reads and weight loads as bf16's 64; the
 // epilogue splits the fp32 result into hi / lo again.
-template <int BC, bool POOL, bool X3 = false>
+// RES (bf16): the epilogue adds a residual tensor (a BasicBlock's identity
+// shortcut: x is added in fp32 to the accumulators the wave already holds,
+// out = bf16(relu(acc + x)), the pooled form sums relu(acc + x)) -- its own
+// instantiations, so the launches without a residual do not carry its loads.
+template <int BC, bool POOL, bool X3 = false, bool RES = false>
 __global__ __launch_bounds__(512, 1) void halo256r_kernel(BlockConvArgs a) {
   using namespace h31;
   constexpr int NCG = BC / 32, NPG = NW / NCG, TP = 16 / NPG;
   static_assert(NCG * NPG == NW && (!POOL || NPG == 1), "wave split");
+  static_assert(!(RES && X3), "the epilogue residual is bf16 only");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -296,7 +303,59 @@ __global__ __launch_bounds__(512, 1) void halo256r_kernel(BlockConvArgs a) {
     const int fr = el & 15, fg = el >> 4;
     const int b = t / tiles_img, rem = t - b * tiles_img;
     const int oy0 = (rem / tiles_x) * TH, ox0 = (rem - (rem / tiles_x) * tiles_x) * TW;
+    // RES: tile rows j, j + 1 of a 16-channel group are ONE 16-B load in the
+    // store layout below (lane rows 0/2: 8 channels of pixel row j, rows 1/3:
+    // of row j + 1), un-swapped into the accumulator layout by the stores' own
+    // v_permlane16_swap (it is its own inverse).  The tile's pixel and the
+    // wave's channels ride in the load's SGPR offset, the channel group in its
+    // immediate.  RB tile rows per batch, two register sets: batch k + 1 is in
+    // flight while batch k is added (and, unpooled, stored).
+    constexpr int RB = 4;
+    h31_v4 rv[2][RB / 2][TC];
+    [[maybe_unused]] auto res_load = [&](int jb, h31_v4 (&v)[RB / 2][TC]) __attribute__((always_inline)) {
+      const __amdgpu_buffer_rsrc_t rr =
+          __builtin_amdgcn_make_buffer_rsrc((void*)a.res, (short)0, (int)a.res_bytes, 0x00020000);
+      const int rps = (int)a.res_pstride * 2;
+      const int rlane = ((fg & 1) * a.W + fr) * rps + (fg >> 1) * 16;
+#pragma unroll
+      for (int jj = 0; jj < RB / 2; ++jj) {
+        const int so = __builtin_amdgcn_readfirstlane(((b * a.H + oy0 + r0w + jb + 2 * jj) * a.W + ox0) * rps + cw * 2);
+#pragma unroll
+        for (int i = 0; i < TC; ++i) v[jj][i] = __builtin_amdgcn_raw_buffer_load_b128(rr, rlane + i * 32, so, 0);
+      }
+    };
+    [[maybe_unused]] auto res_add = [&](int jb, const h31_v4 (&v)[RB / 2][TC]) __attribute__((always_inline)) {
+#pragma unroll
+      for (int jj = 0; jj < RB / 2; ++jj)
+#pragma unroll
+        for (int i = 0; i < TC; ++i) {
+          uint32_t q[4] = {v[jj][i][0], v[jj][i][1], v[jj][i][2], v[jj][i][3]};
+#pragma unroll
+          for (int e = 0; e < 2; ++e) {
+            const auto r = __builtin_amdgcn_permlane16_swap(q[e], q[e + 2], false, false);
+            q[e] = r[0];
+            q[e + 2] = r[1];
+          }
+          // q[0..1]: this lane's 4 channels of row j, q[2..3]: of row j + 1
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            f32x4& c = acc[i][jb + 2 * jj + (e >> 1)];
+            c[2 * (e & 1)] += __uint_as_float(q[e] << 16);
+            c[2 * (e & 1) + 1] += __uint_as_float(q[e] & 0xFFFF0000u);
+          }
+        }
+    };
+    // batch jb: the next batch's loads first, then this batch's adds
+    [[maybe_unused]] auto res_batch = [&](int jb) __attribute__((always_inline)) {
+      if (jb + RB < TP) res_load(jb + RB, rv[(jb / RB + 1) & 1]);
+      res_add(jb, rv[(jb / RB) & 1]);
+    };
+    if constexpr (RES) res_load(0, rv[0]);
     if constexpr (POOL) {
+      if constexpr (RES) {
+#pragma unroll
+        for (int jb = 0; jb < TP; jb += RB) res_batch(jb);
+      }
       // the wave holds all 256 pixels of its channels: relu(acc) (the bias is
       // in acc) summed over its 16 row fragments, then over the 16 lanes of a
       // row (DPP)
@@ -322,6 +381,9 @@ __global__ __launch_bounds__(512, 1) void halo256r_kernel(BlockConvArgs a) {
       u16* __restrict__ out = (u16*)a.out;
 #pragma unroll
       for (int j = 0; j < TP; j += 2) {
+        if constexpr (RES) {
+          if (j % RB == 0) res_batch(j);
+        }
         const int64_t px = (int64_t)(b * a.H + oy0 + r0w + j + (fg & 1)) * a.W + ox0 + fr;
 #pragma unroll
         for (int i = 0; i < TC; ++i) {
@@ -436,12 +498,12 @@ __global__ __launch_bounds__(512, 1) void halo256r_kernel(BlockConvArgs a) {
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
-template <int BC, bool POOL, bool X3>
+template <int BC, bool POOL, bool X3, bool RES = false>
 static int launch_halo256r_t(const BlockConvArgs& a, hipStream_t s) {
   using namespace h31;
   static bool attr = false;
   if (!attr) {
-    (void)hipFuncSetAttribute((const void*)halo256r_kernel<BC, POOL, X3>,
+    (void)hipFuncSetAttribute((const void*)halo256r_kernel<BC, POOL, X3, RES>,
                               hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
     attr = true;
   }
@@ -449,7 +511,7 @@ static int launch_halo256r_t(const BlockConvArgs& a, hipStream_t s) {
   const int64_t tiles_p = (int64_t)a.N * (a.H / TH) * (a.W / TW);
   int64_t g = std::min<int64_t>(tiles_p * n_tc, 256);
   g = std::max<int64_t>(n_tc, g / n_tc * n_tc);
-  hipLaunchKernelGGL((halo256r_kernel<BC, POOL, X3>), dim3((unsigned)g), dim3(512), SMEM, s, a);
+  hipLaunchKernelGGL((halo256r_kernel<BC, POOL, X3, RES>), dim3((unsigned)g), dim3(512), SMEM, s, a);
   SAD_CHECK_HIP(hipGetLastError());
   return SAD_OK;
 }
@@ -459,7 +521,12 @@ static int launch_halo256r_t(const BlockConvArgs& a, hipStream_t s) {
 // Cout and the bias logical)
 int launch_halo256r(const BlockConvArgs& a, hipStream_t s, bool x3) {
   SAD_REQUIRE(a.KH == 3 && a.KW == 3 && a.stride == 1 && a.pad == 1, "variant 31: 3x3, stride 1, pad 1");
-  SAD_REQUIRE(!a.res && !a.st_part, "variant 31: no epilogue residual / fused statistics (shortcut as in1)");
+  SAD_REQUIRE(!a.st_part, "variant 31: no fused statistics");
+  SAD_REQUIRE(!a.res || (!x3 && !a.in1),
+              "variant 31: the epilogue residual is bf16 only and excludes a shortcut source (split-bf16: shortcut as in1)");
+  SAD_REQUIRE(!a.res || (a.res_pstride >= a.Cout && a.res_pstride % 8 == 0 && ((uintptr_t)a.res & 15) == 0 &&
+                         a.res_bytes == ((a.M - 1) * a.res_pstride + a.Cout) * 2 && a.res_bytes < (1ll << 31) - 65536),
+              "variant 31: residual [M, res_pstride] bf16, 16-B aligned pixels, within the 2 GiB buffer range");
   SAD_REQUIRE(a.Cout % 128 == 0, "variant 31: Cout must be a multiple of 128");
   SAD_REQUIRE(a.H % 16 == 0 && a.W % 16 == 0 && a.Ho == a.H && a.Wo == a.W, "variant 31: image must tile by 16 x 16");
   SAD_REQUIRE((a.Cin * 2) % 128 == 0 && (!a.in1 || (a.Cin1 * 2) % 128 == 0), "variant 31: whole 128-B chunks");
@@ -475,8 +542,12 @@ int launch_halo256r(const BlockConvArgs& a, hipStream_t s, bool x3) {
   if (a.pool_out) {
     SAD_REQUIRE(a.H == 16 && a.W == 16 && a.Cout % 256 == 0,
                 "variant 31 fused average pool: a 16 x 16 tile must be one image, Cout % 256");
+    if (a.res) return launch_halo256r_t<256, true, false, true>(a, s);
     return x3 ? launch_halo256r_t<256, true, true>(a, s) : launch_halo256r_t<256, true, false>(a, s);
   }
+  if (a.res)
+    return a.Cout % 256 == 0 ? launch_halo256r_t<256, false, false, true>(a, s)
+                             : launch_halo256r_t<128, false, false, true>(a, s);
   if (x3)
     return a.Cout % 256 == 0 ? launch_halo256r_t<256, false, true>(a, s) : launch_halo256r_t<128, false, true>(a, s);
   return a.Cout % 256 == 0 ? launch_halo256r_t<256, false, false>(a, s) : launch_halo256r_t<128, false, false>(a, s);

@@ -60,7 +60,7 @@ struct BlockConvArgs {
   const void* wt;        // [Cout][wt_ld] (dtype): KH*KW*Cin conv taps, then Cin1 shortcut columns
   int wt_ld;             // elements per weight row; 0 = KH*KW*Cin + Cin1
   const float* bias;     // [Cout]
-  const void* res;       // optional residual added before the activation, NHWC [M, *] (halo kernel only)
+  const void* res;       // optional residual added before the activation, NHWC [M, *] (halo kernels, variants 13, 31, 41)
   int64_t res_pstride;
   void* out;             // [M, *] pixel stride out_pstride
   int64_t out_pstride;
@@ -129,6 +129,7 @@ int default_block_variant(const BlockConvArgs& a, int dtype);
 int gemm_block_variant(const BlockConvArgs& a);  // default_block_variant without 30/31 (bf16)
 bool layer2_halo();
 bool x3_layer2_v31();  // SAD_X3_L2_V31 (default 1): split-bf16 layer2 stride-1 convs on variant 31 (128-channel tiles)
+bool v31_identity_residual(int dtype, int cout, int Ho);  // bf16 layer3/4 identity blocks: the shortcut as variant 31's epilogue residual
 bool layer2_v31();  // SAD_L2_V31 (default 0; 1: measured 2.2-2.7 % slower): layer2's stride-1 convs on variant 31 (128-channel tiles)
 bool block_conv_can_pool(const BlockConvArgs& a, int dtype);  // default variant pools Ho x Wo tiles  // SAD_L2_HALO (default 1): layer2's identity blocks on the halo kernel
 // dx (+)= col2im(dcol) (train.hip; the strided dgrad of wgrad.hip)

@@ -261,12 +261,15 @@ static int rn_block_conv(const sad_resnet_plan* p, const ConvW& c, const void* x
 // BasicBlock conv2 whose identity shortcut goes in as an epilogue residual
 // (ResNet-18's plan, api.hip run_blocks): stride 1, no downsample, 16 x 16
 // tiles, Cout <= 64, or Cout <= 128 where layer2 runs the halo / resident-weight
-// kernels (the split-bf16 mode's variant 31 takes the identity as K columns)
+// kernels, or (bf16) Cout a multiple of 256 where layer3/4 run variant 31,
+// which adds it in fp32 to the accumulators (the split-bf16 mode's variants
+// 30 / 31 take the identity as K columns)
 static bool identity_epilogue(const sad_resnet_plan* p, const Block& b, int Ho) {
   const int dtype = p->dtype;
   if (p->x4 || !(dtype == SAD_BF16 || dtype == SAD_BF16X3) || b.stride != 1 || b.has_ds || Ho % 16 != 0) return false;
   return b.cout <= 64 || (b.cout <= 128 && layer2_halo() && !(dtype == SAD_BF16 && layer2_v31()) &&
-                          !(dtype == SAD_BF16X3 && x3_layer2_v31()));
+                          !(dtype == SAD_BF16X3 && x3_layer2_v31())) ||
+         v31_identity_residual(dtype, b.cout, Ho);
 }
 
 static int rn_chunk(const sad_resnet_plan* p, const float* map, const float* img, int64_t n, float* feats, char* ws,
@@ -302,9 +305,9 @@ static int rn_chunk(const sad_resnet_plan* p, const float* map, const float* img
       } else {
         if ((rc = rn_block_conv(p, b.c1, X, n, H, b.stride, nullptr, 0, 0, 1, T1, s))) return rc;
         if (identity_epilogue(p, b, Ho)) {
-          // identity blocks of layer1/2: the shortcut as an epilogue add on the
-          // halo / resident-weight kernels (as ResNet-18's plan), not as identity
-          // K columns on the implicit GEMM
+          // identity blocks of layer1/2 (and bf16 layer3/4): the shortcut as an
+          // epilogue add on the halo / resident-weight kernels / variant 31 (as
+          // ResNet-18's plan), not as identity K columns
           if ((rc = rn_block_conv(p, b.c2, T1, n, Ho, 1, nullptr, 0, 0, 1, Y, s, X))) return rc;
         } else {
           if ((rc = rn_block_conv(p, b.c2, T1, n, Ho, 1, X, H, C, b.stride, Y, s))) return rc;
