@@ -282,6 +282,42 @@ int sad_backbone_run_debug(const sad_backbone_plan* plan, const float* map, int6
                            float* feats, void* layer4_out, void* workspace, size_t ws_bytes,
                            void* stream);
 
+/* Shared-trunk ensembles: the ResNet-18 plan split after layer3.  Reference
+ * training only ever changes layer4 and the head, so sub-models trained on one
+ * frozen trunk differ in layer4 alone: the trunk (stem, layer1-3; 13.83 of the
+ * 18.13 GFLOP per segment) runs once and each sub-model's tail (layer4 +
+ * average pool) runs on its output.  Every sub-model keeps a full
+ * sad_backbone_plan; an entry uses the part of the plan it names.  Trunk and
+ * tail issue exactly the launches sad_backbone_run* issues for their part on
+ * the same micro-batch, so trunk_run followed by tail_run equals
+ * sad_backbone_run / sad_backbone_run_img bit for bit.
+ *
+ * l3: layer3's output, NHWC [B, 32, 32, 256] in the plan's activation layout:
+ *   SAD_BF16    bf16, 256 values per pixel (512 B)
+ *   SAD_F32     fp32, 256 values per pixel (1 KiB)
+ *   SAD_BF16X3  split-bf16, 512 bf16 per pixel (1 KiB): per group of 32
+ *               channels [hi(32) | lo(32)], hi = bf16(x), lo = bf16(x - hi)
+ * Exactly one of map ([B, map_h, map_w] fp32) and img ([B, 512, 512] fp32, as
+ * sad_backbone_run_img) is non-null.  trunk_run and tail_run take a workspace
+ * of sad_backbone_workspace_size(micro_batch) bytes. */
+int sad_backbone_trunk_run(const sad_backbone_plan* plan, const float* map, const float* img,
+                           int64_t B, int64_t micro_batch, void* l3_out, void* workspace,
+                           size_t ws_bytes, void* stream);
+/* layer4 + average pool of `plan` on l3 -> feats [B, 512] fp32; l3 is only read. */
+int sad_backbone_tail_run(const sad_backbone_plan* plan, const void* l3, int64_t B,
+                          int64_t micro_batch, float* feats, void* workspace, size_t ws_bytes,
+                          void* stream);
+/* Per micro-batch chunk: the trunk of trunk_plan once, then the tail of each
+ * of tail_plans[0..n_tails) on it -> feats[t] [B, 512] fp32.  Tails must have
+ * the trunk's dtype and map size (SAD_ERR_ARG otherwise).  The workspace holds
+ * the chunk's layer3 activation beside the run's buffers. */
+int sad_backbone_shared_workspace_size(const sad_backbone_plan* trunk_plan, int64_t micro_batch,
+                                       size_t* bytes);
+int sad_backbone_shared_run(const sad_backbone_plan* trunk_plan,
+                            const sad_backbone_plan* const* tail_plans, int32_t n_tails,
+                            const float* map, const float* img, int64_t B, int64_t micro_batch,
+                            float* const* feats, void* workspace, size_t ws_bytes, void* stream);
+
 /* Deeper timm ResNets (resnet34/50/101/152, the
  * `--model-name` choices of submodel_trainer.py:51 / model_merger.py:24 /
  * inference_runner.py:77 backbone_name), on the same kernels: fused

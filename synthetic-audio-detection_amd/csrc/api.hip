@@ -527,6 +527,123 @@ static int front_sub_batch(int dtype) {
   return dtype == SAD_BF16 && l1_fused() ? 256 : dtype == SAD_BF16X3 ? 64 : 32;
 }
 
+// Stem + layer1 of the block path on mb segments, per sub-chunk of
+// front_sub_batch segments; layer1's output [mb, 128, 128, 64] is gathered in bufD.
+static int run_front(const sad_backbone_plan* p, const float* map, const float* img, const float* img3, int64_t mb,
+                     void* bufA, void* bufB, void* bufT, void* bufD, int& H, int& C, hipStream_t s) {
+  int rc;
+  const size_t es = p->dtype == SAD_BF16 ? 2 : 4;
+  const int64_t f = front_sub_batch(p->dtype) > 0 ? std::min<int64_t>(front_sub_batch(p->dtype), mb) : mb;
+  // stem + layer1 per sub-chunk of f segments (Infinity-Cache-sized); layer1's
+  // output ([f, 128, 128, 64] per sub-chunk) is gathered in bufD, then layers
+  // 2-4 run on the whole micro-batch (layer2's halo grids underfill at f = 32:
+  // its two convs took 218 + 201 vs 197 + 185 us per 128 segments).
+  const size_t l1_elems = 128 * 128 * 64;
+  for (int64_t i = 0; i < mb; i += f) {
+    const int64_t n = std::min(f, mb - i);
+    void* a0 = bufA;
+    void* a1 = bufB;
+    StemArgs st{map ? map + i * p->mh * p->mw : nullptr, img ? img + i * 512 * 512 : nullptr, p->mh, p->mw,
+                p->stem_w, p->stem_b, a0, n, img3 ? img3 + i * 3 * 512 * 512 : nullptr, p->stem_w3};
+    if ((rc = launch_stem(st, p->dtype, s))) return rc;
+    H = 128;
+    C = 64;
+    if ((rc = run_blocks(p, 0, 1, n, &a0, &a1, bufT, H, C, s))) return rc;
+    // layer1's second block writes straight into its slot of bufD
+    void* slot = (char*)bufD + (size_t)i * l1_elems * es;
+    void* dst = slot;
+    void* src = a0;
+    if ((rc = run_blocks(p, 1, 2, n, &src, &dst, bufT, H, C, s))) return rc;
+    if (src != slot) {
+      set_error("internal: layer1 output not in its bufD slot");
+      return SAD_ERR_STATE;
+    }
+  }
+  return SAD_OK;
+}
+
+// BasicBlocks [b0, b1) of the first-generation per-conv path (fp32 / bf16):
+// *in -> *in (the last output; *in and *alt swap per block, tmp holds conv1's
+// output and dsbuf the downsample's).
+static int run_convs(const sad_backbone_plan* p, size_t b0, size_t b1, int64_t mb, void** in, void** alt, void* tmp,
+                     void* dsbuf, int& H, int& C, hipStream_t s) {
+  int rc;
+  void* bufA = *in;
+  void* bufB = *alt;
+  void* bufT = tmp;
+  void* bufD = dsbuf;
+  size_t ci = 0;
+  for (size_t bi = 0; bi < b0; ++bi) ci += (bi % 2 == 0 && bi >= 2) ? 3 : 2;
+  for (size_t bi = b0; bi < b1; ++bi) {
+    const DevConv& c1 = p->convs[ci++];
+    const DevConv& c2 = p->convs[ci++];
+    const DevConv* ds = nullptr;
+    if (bi % 2 == 0 && bi >= 2) ds = &p->convs[ci++];
+    const int Ho = H / c1.spec.stride;
+    ConvArgs a{};
+    a.in = bufA;
+    a.in_pstride = C;
+    a.N = (int)mb;
+    a.H = H;
+    a.W = H;
+    a.Cin = C;
+    a.wt = c1.w;
+    a.bias = c1.bias;
+    a.res = nullptr;
+    a.out = bufT;
+    a.out_pstride = c1.spec.cout;
+    a.Ho = Ho;
+    a.Wo = Ho;
+    a.Cout = c1.spec.cout;
+    a.KH = a.KW = c1.spec.k;
+    a.stride = c1.spec.stride;
+    a.pad = c1.spec.pad;
+    a.relu = 1;
+    a.M = mb * Ho * Ho;
+    if ((rc = launch_conv(a, p->dtype, s))) return rc;
+    const void* res = bufA;
+    if (ds) {
+      ConvArgs d = a;
+      d.wt = ds->w;
+      d.bias = ds->bias;
+      d.out = bufD;
+      d.KH = d.KW = 1;
+      d.pad = 0;
+      d.relu = 0;
+      if ((rc = launch_conv(d, p->dtype, s))) return rc;
+      res = bufD;
+    }
+    ConvArgs a2{};
+    a2.in = bufT;
+    a2.in_pstride = c2.spec.cin;
+    a2.N = (int)mb;
+    a2.H = Ho;
+    a2.W = Ho;
+    a2.Cin = c2.spec.cin;
+    a2.wt = c2.w;
+    a2.bias = c2.bias;
+    a2.res = res;
+    a2.res_pstride = c2.spec.cout;
+    a2.out = bufB;
+    a2.out_pstride = c2.spec.cout;
+    a2.Ho = Ho;
+    a2.Wo = Ho;
+    a2.Cout = c2.spec.cout;
+    a2.KH = a2.KW = 3;
+    a2.stride = 1;
+    a2.pad = 1;
+    a2.relu = 1;
+    a2.M = mb * Ho * Ho;
+    if ((rc = launch_conv(a2, p->dtype, s))) return rc;
+    std::swap(bufA, bufB);
+    H = Ho;
+    C = c2.spec.cout;
+  }
+  *in = bufA;
+  *alt = bufB;
+  return SAD_OK;
+}
+
 static int run_chunk(const sad_backbone_plan* p, const float* map, const float* img, int64_t mb, float* feats,
                      void* layer4_out, char* ws, hipStream_t s, const float* img3 = nullptr) {
   const size_t ab = act_bytes(p, mb);
@@ -538,33 +655,7 @@ static int run_chunk(const sad_backbone_plan* p, const float* map, const float* 
   int H = 128, C = 64;
   bool pooled = false;  // the last conv wrote the pooled features itself
   if (p->block_path) {
-    const size_t es = p->dtype == SAD_BF16 ? 2 : 4;
-    const int64_t f = front_sub_batch(p->dtype) > 0 ? std::min<int64_t>(front_sub_batch(p->dtype), mb) : mb;
-    // stem + layer1 per sub-chunk of f segments (Infinity-Cache-sized); layer1's
-    // output ([f, 128, 128, 64] per sub-chunk) is gathered in bufD, then layers
-    // 2-4 run on the whole micro-batch (layer2's halo grids underfill at f = 32:
-    // its two convs took 218 + 201 vs 197 + 185 us per 128 segments).
-    const size_t l1_elems = 128 * 128 * 64;
-    for (int64_t i = 0; i < mb; i += f) {
-      const int64_t n = std::min(f, mb - i);
-      void* a0 = bufA;
-      void* a1 = bufB;
-      StemArgs st{map ? map + i * p->mh * p->mw : nullptr, img ? img + i * 512 * 512 : nullptr, p->mh, p->mw,
-                  p->stem_w, p->stem_b, a0, n, img3 ? img3 + i * 3 * 512 * 512 : nullptr, p->stem_w3};
-      if ((rc = launch_stem(st, p->dtype, s))) return rc;
-      H = 128;
-      C = 64;
-      if ((rc = run_blocks(p, 0, 1, n, &a0, &a1, bufT, H, C, s))) return rc;
-      // layer1's second block writes straight into its slot of bufD
-      void* slot = (char*)bufD + (size_t)i * l1_elems * es;
-      void* dst = slot;
-      void* src = a0;
-      if ((rc = run_blocks(p, 1, 2, n, &src, &dst, bufT, H, C, s))) return rc;
-      if (src != slot) {
-        set_error("internal: layer1 output not in its bufD slot");
-        return SAD_ERR_STATE;
-      }
-    }
+    if ((rc = run_front(p, map, img, img3, mb, bufA, bufB, bufT, bufD, H, C, s))) return rc;
     void* a0 = bufD;
     void* a1 = bufA;
     if ((rc = run_blocks(p, 2, p->blocks.size(), mb, &a0, &a1, bufB, H, C, s, layer4_out ? nullptr : feats,
@@ -574,74 +665,7 @@ static int run_chunk(const sad_backbone_plan* p, const float* map, const float* 
   } else {
     StemArgs st{map, img, p->mh, p->mw, p->stem_w, p->stem_b, bufA, mb, img3, p->stem_w3};
     if ((rc = launch_stem(st, p->dtype, s))) return rc;
-  }
-  size_t ci = 0;
-  for (int li = 0; li < 4 && !p->block_path; ++li) {
-    for (int b = 0; b < 2; ++b) {
-      const DevConv& c1 = p->convs[ci++];
-      const DevConv& c2 = p->convs[ci++];
-      const DevConv* ds = nullptr;
-      if (b == 0 && li > 0) ds = &p->convs[ci++];
-      const int Ho = H / c1.spec.stride;
-      ConvArgs a{};
-      a.in = bufA;
-      a.in_pstride = C;
-      a.N = (int)mb;
-      a.H = H;
-      a.W = H;
-      a.Cin = C;
-      a.wt = c1.w;
-      a.bias = c1.bias;
-      a.res = nullptr;
-      a.out = bufT;
-      a.out_pstride = c1.spec.cout;
-      a.Ho = Ho;
-      a.Wo = Ho;
-      a.Cout = c1.spec.cout;
-      a.KH = a.KW = c1.spec.k;
-      a.stride = c1.spec.stride;
-      a.pad = c1.spec.pad;
-      a.relu = 1;
-      a.M = mb * Ho * Ho;
-      if ((rc = launch_conv(a, p->dtype, s))) return rc;
-      const void* res = bufA;
-      if (ds) {
-        ConvArgs d = a;
-        d.wt = ds->w;
-        d.bias = ds->bias;
-        d.out = bufD;
-        d.KH = d.KW = 1;
-        d.pad = 0;
-        d.relu = 0;
-        if ((rc = launch_conv(d, p->dtype, s))) return rc;
-        res = bufD;
-      }
-      ConvArgs a2{};
-      a2.in = bufT;
-      a2.in_pstride = c2.spec.cin;
-      a2.N = (int)mb;
-      a2.H = Ho;
-      a2.W = Ho;
-      a2.Cin = c2.spec.cin;
-      a2.wt = c2.w;
-      a2.bias = c2.bias;
-      a2.res = res;
-      a2.res_pstride = c2.spec.cout;
-      a2.out = bufB;
-      a2.out_pstride = c2.spec.cout;
-      a2.Ho = Ho;
-      a2.Wo = Ho;
-      a2.Cout = c2.spec.cout;
-      a2.KH = a2.KW = 3;
-      a2.stride = 1;
-      a2.pad = 1;
-      a2.relu = 1;
-      a2.M = mb * Ho * Ho;
-      if ((rc = launch_conv(a2, p->dtype, s))) return rc;
-      std::swap(bufA, bufB);
-      H = Ho;
-      C = c2.spec.cout;
-    }
+    if ((rc = run_convs(p, 0, 8, mb, &bufA, &bufB, bufT, bufD, H, C, s))) return rc;
   }
   if (layer4_out) {
     const size_t es = p->dtype == SAD_BF16 ? 2 : 4;
@@ -649,6 +673,165 @@ static int run_chunk(const sad_backbone_plan* p, const float* map, const float* 
   }
   if (pooled) return SAD_OK;
   return launch_avgpool(bufA, mb, H * H, C, feats, p->dtype, s);
+}
+
+// ---- shared-trunk ensembles: the backbone split after layer3.  The trunk
+// (stem, layer1-3) and the tail (layer4 + average pool) issue exactly the
+// launches run_chunk issues for their part, on the same micro-batch, so
+// trunk + tail is bit-identical to sad_backbone_run*.
+static constexpr int64_t kL3Elems = 32ll * 32 * 256;  // per segment, layer3 output
+static size_t l3_bytes(const sad_backbone_plan* p, int64_t n) {
+  return (size_t)n * kL3Elems * (p->dtype == SAD_BF16 ? 2 : 4);
+}
+
+// stem .. layer3 on mb segments -> l3_out [mb, 32, 32, 256] (plan layout)
+static int trunk_chunk(const sad_backbone_plan* p, const float* map, const float* img, int64_t mb, void* l3_out,
+                       char* ws, hipStream_t s) {
+  const size_t ab = act_bytes(p, mb);
+  void* bufA = ws;
+  void* bufB = ws + ab;
+  void* bufT = ws + 2 * ab;
+  void* bufD = ws + 3 * ab;
+  int rc;
+  int H = 128, C = 64;
+  void* src;
+  void* dst = l3_out;
+  if (p->block_path) {
+    if ((rc = run_front(p, map, img, nullptr, mb, bufA, bufB, bufT, bufD, H, C, s))) return rc;
+    void* a0 = bufD;
+    void* a1 = bufA;
+    if ((rc = run_blocks(p, 2, 5, mb, &a0, &a1, bufB, H, C, s))) return rc;
+    // layer3's second block writes straight into l3_out
+    src = a0;
+    if ((rc = run_blocks(p, 5, 6, mb, &src, &dst, bufB, H, C, s))) return rc;
+  } else {
+    StemArgs st{map, img, p->mh, p->mw, p->stem_w, p->stem_b, bufA, mb, nullptr, p->stem_w3};
+    if ((rc = launch_stem(st, p->dtype, s))) return rc;
+    if ((rc = run_convs(p, 0, 5, mb, &bufA, &bufB, bufT, bufD, H, C, s))) return rc;
+    src = bufA;
+    if ((rc = run_convs(p, 5, 6, mb, &src, &dst, bufT, bufD, H, C, s))) return rc;
+  }
+  if (src != l3_out || H != 32 || C != 256) {
+    set_error("internal: layer3 output not in l3_out");
+    return SAD_ERR_STATE;
+  }
+  return SAD_OK;
+}
+
+// layer4 + average pool on l3 [mb, 32, 32, 256] (read only) -> feats [mb, 512].
+// The two blocks run as two calls so that the second writes a workspace
+// buffer, not the first one's input.
+static int tail_chunk(const sad_backbone_plan* p, const void* l3, int64_t mb, float* feats, char* ws,
+                      hipStream_t s) {
+  const size_t ab = act_bytes(p, mb);
+  void* bufX = ws;
+  void* bufY = ws + ab;
+  void* bufT = ws + 2 * ab;
+  void* bufD = ws + 3 * ab;
+  int rc;
+  int H = 32, C = 256;
+  bool pooled = false;
+  void* src = const_cast<void*>(l3);
+  void* dst = bufX;
+  if (p->block_path) {
+    if ((rc = run_blocks(p, 6, 7, mb, &src, &dst, bufT, H, C, s))) return rc;
+    dst = bufY;
+    if ((rc = run_blocks(p, 7, 8, mb, &src, &dst, bufT, H, C, s, feats, &pooled))) return rc;
+  } else {
+    if ((rc = run_convs(p, 6, 7, mb, &src, &dst, bufT, bufD, H, C, s))) return rc;
+    dst = bufY;
+    if ((rc = run_convs(p, 7, 8, mb, &src, &dst, bufT, bufD, H, C, s))) return rc;
+  }
+  if (pooled) return SAD_OK;
+  if (src != bufY) {
+    set_error("internal: layer4 output not in its workspace buffer");
+    return SAD_ERR_STATE;
+  }
+  return launch_avgpool(src, mb, H * H, C, feats, p->dtype, s);
+}
+
+extern "C" int sad_backbone_trunk_run(const sad_backbone_plan* p, const float* map, const float* img, int64_t B,
+                                      int64_t mb, void* l3_out, void* ws, size_t ws_bytes, void* stream) {
+  SAD_REQUIRE(p && l3_out && ws, "null args");
+  SAD_REQUIRE((map != nullptr) != (img != nullptr), "exactly one of map and img must be given");
+  SAD_REQUIRE(B >= 0 && mb > 0, "bad batch");
+  SAD_REQUIRE(p->blocks.size() == 8, "not a ResNet-18 plan");
+  size_t need = 0;
+  sad_backbone_workspace_size(p, mb, &need);
+  if (ws_bytes < need) {
+    set_error("workspace too small");
+    return SAD_ERR_NOMEM;
+  }
+  const int64_t plane = map ? (int64_t)p->mh * p->mw : 512 * 512;
+  const float* x = map ? map : img;
+  for (int64_t i = 0; i < B; i += mb) {
+    const int64_t n = std::min(mb, B - i);
+    const float* xi = x + i * plane;
+    int rc = trunk_chunk(p, map ? xi : nullptr, map ? nullptr : xi, n, (char*)l3_out + l3_bytes(p, i), (char*)ws,
+                         (hipStream_t)stream);
+    if (rc) return rc;
+  }
+  return SAD_OK;
+}
+
+extern "C" int sad_backbone_tail_run(const sad_backbone_plan* p, const void* l3, int64_t B, int64_t mb,
+                                     float* feats, void* ws, size_t ws_bytes, void* stream) {
+  SAD_REQUIRE(p && l3 && feats && ws, "null args");
+  SAD_REQUIRE(B >= 0 && mb > 0, "bad batch");
+  SAD_REQUIRE(p->blocks.size() == 8, "not a ResNet-18 plan");
+  size_t need = 0;
+  sad_backbone_workspace_size(p, mb, &need);
+  if (ws_bytes < need) {
+    set_error("workspace too small");
+    return SAD_ERR_NOMEM;
+  }
+  for (int64_t i = 0; i < B; i += mb) {
+    const int64_t n = std::min(mb, B - i);
+    int rc = tail_chunk(p, (const char*)l3 + l3_bytes(p, i), n, feats + i * 512, (char*)ws, (hipStream_t)stream);
+    if (rc) return rc;
+  }
+  return SAD_OK;
+}
+
+extern "C" int sad_backbone_shared_workspace_size(const sad_backbone_plan* p, int64_t mb, size_t* bytes) {
+  SAD_REQUIRE(p && bytes && mb > 0, "bad args");
+  *bytes = 4 * act_bytes(p, mb) + ((l3_bytes(p, mb) + 255) & ~(size_t)255);
+  return SAD_OK;
+}
+
+extern "C" int sad_backbone_shared_run(const sad_backbone_plan* trunk, const sad_backbone_plan* const* tails,
+                                       int32_t n_tails, const float* map, const float* img, int64_t B, int64_t mb,
+                                       float* const* feats, void* ws, size_t ws_bytes, void* stream) {
+  SAD_REQUIRE(trunk && tails && feats && ws, "null args");
+  SAD_REQUIRE(n_tails > 0, "n_tails must be positive");
+  SAD_REQUIRE((map != nullptr) != (img != nullptr), "exactly one of map and img must be given");
+  SAD_REQUIRE(B >= 0 && mb > 0, "bad batch");
+  SAD_REQUIRE(trunk->blocks.size() == 8, "not a ResNet-18 plan");
+  for (int t = 0; t < n_tails; ++t) {
+    SAD_REQUIRE(tails[t] && feats[t], "null tail plan or feature pointer");
+    SAD_REQUIRE(tails[t]->blocks.size() == 8, "tail is not a ResNet-18 plan");
+    SAD_REQUIRE(tails[t]->dtype == trunk->dtype, "tail plan dtype differs from the trunk's");
+    SAD_REQUIRE(tails[t]->mh == trunk->mh && tails[t]->mw == trunk->mw, "tail plan map size differs from the trunk's");
+    SAD_REQUIRE(tails[t]->block_path == trunk->block_path, "tail plan path differs from the trunk's");
+  }
+  size_t need = 0;
+  sad_backbone_shared_workspace_size(trunk, mb, &need);
+  if (ws_bytes < need) {
+    set_error("workspace too small");
+    return SAD_ERR_NOMEM;
+  }
+  void* l3 = (char*)ws + 4 * act_bytes(trunk, mb);
+  const int64_t plane = map ? (int64_t)trunk->mh * trunk->mw : 512 * 512;
+  const float* x = map ? map : img;
+  for (int64_t i = 0; i < B; i += mb) {
+    const int64_t n = std::min(mb, B - i);
+    const float* xi = x + i * plane;
+    int rc = trunk_chunk(trunk, map ? xi : nullptr, map ? nullptr : xi, n, l3, (char*)ws, (hipStream_t)stream);
+    if (rc) return rc;
+    for (int t = 0; t < n_tails; ++t)
+      if ((rc = tail_chunk(tails[t], l3, n, feats[t] + i * 512, (char*)ws, (hipStream_t)stream))) return rc;
+  }
+  return SAD_OK;
 }
 
 extern "C" int sad_backbone_run(const sad_backbone_plan* p, const float* map, int64_t B, int64_t mb,

@@ -154,7 +154,7 @@ class ModularMultiHeadClassifier:
         if torch.equal(x[:, 0], x[:, 1]) and torch.equal(x[:, 0], x[:, 2]):
             # the spectrogram path (repeat(3), :173): conv1 folded over the channels
             img = x[:, 0].contiguous()
-            feats = [bb.forward_images(img) for bb in eng.backbones]
+            feats = eng.features(img, kind='img')
         else:  # any other tensor (e.g. the load-time randn(2,3,512,512) check, :119-122)
             img3 = x.contiguous()
             feats = [bb.forward_images3(img3) for bb in eng.backbones]
@@ -204,6 +204,8 @@ def load_merged_model(merged_path: str, device: torch.device, backbone_name='res
     # of the reference's own random [2, 3, 512, 512] input (distinct channels).
     dummy = final_model(torch.randn(2, 3, 512, 512))
     print('Rebuilt merged model => dummy output shape:', dummy.shape)
+    # what the ensemble costs: distinct trunks (stem..layer3) and layer4 tails
+    print(final_model.engine.grouping.describe())
     return final_model, metadata
 
 

@@ -41,12 +41,37 @@ def force_separate_parameters(model):
         model._sd[k] = v.clone()
 
 
-def load_sub_model(checkpoint_path, device, model_name='resnet18'):
-    """model_merger.py:46-59: BinaryClassifier + strict=False load of ck['state_dict']."""
-    model = BinaryClassifier(model_name=model_name)
+def to_base_keys(sd_in):
+    """Trainer checkpoint keys (unprefixed timm keys + ``head.*``) ->
+    ``base.*`` / ``head.*``; a state dict already in ``base.*`` form is returned
+    as it is."""
+    if any(k.startswith('base.') for k in sd_in):
+        return dict(sd_in)
+    return {(k if k.startswith('head.') else f'base.{k}'): v for k, v in sd_in.items()}
+
+
+def load_sub_model(checkpoint_path, device, model_name='resnet18', keep_backbone=False):
+    """model_merger.py:46-59: BinaryClassifier + strict=False load of ck['state_dict'].
+
+    keep_backbone=True (``--keep-backbone``) keeps the trained backbone instead
+    (quirk C2 off): the trainer's keys are mapped to ``base.*`` and loaded
+    strictly -- every backbone tensor and buffer (``num_batches_tracked``
+    included) and every ``head.*`` key must be there, RuntimeError otherwise."""
     ck = torch.load(checkpoint_path, map_location='cpu', weights_only=True)
     sd_in = ck['state_dict']
-    model.load_state_dict(sd_in, strict=False)
+    if keep_backbone:
+        model = BinaryClassifier(model_name=model_name, init='empty')
+        sd_in = to_base_keys(sd_in)
+        want = model.state_dict()
+        missing = [k for k in want if k not in sd_in]
+        unexpected = [k for k in sd_in if k not in want]
+        if missing or unexpected:
+            raise RuntimeError(f'{checkpoint_path}: --keep-backbone needs the whole {model_name} sub-model: '
+                               f'missing keys {missing}, unexpected keys {unexpected}')
+        model.load_state_dict(sd_in, strict=True)
+    else:
+        model = BinaryClassifier(model_name=model_name)
+        model.load_state_dict(sd_in, strict=False)
     force_separate_parameters(model)
     return model
 
@@ -61,14 +86,14 @@ def merged_real_class(real_names):
     return name
 
 
-def merge(entries, submodels_folder, model_name='resnet18', device='cpu'):
+def merge(entries, submodels_folder, model_name='resnet18', device='cpu', keep_backbone=False):
     """CSV rows (dicts) -> (ModularMultiHeadClassifier, class_names)."""
     sub_models, synthetic_names, real_names = [], [], []
     for i, entry in enumerate(entries, start=1):
         model_path = os.path.join(submodels_folder, entry['model_filename'])
         print(f"Loading sub-model {i} from {model_path} with synthetic class '{entry['synthetic_class']}' "
               f"and real class '{entry['real_class']}'")
-        sub_models.append(load_sub_model(model_path, device, model_name=model_name))
+        sub_models.append(load_sub_model(model_path, device, model_name=model_name, keep_backbone=keep_backbone))
         synthetic_names.append(entry['synthetic_class'])
         real_names.append(entry['real_class'])
     merged = ModularMultiHeadClassifier(sub_models, device if str(device).startswith('cuda') else 'cuda')
@@ -82,6 +107,9 @@ def main(argv=None):
                         help='CSV file with columns "model_filename", "synthetic_class", and "real_class".')
     parser.add_argument('--model-name', type=str, default='resnet18')
     parser.add_argument('--output-path', type=str, required=True)
+    parser.add_argument('--keep-backbone', action='store_true',
+                        help='keep each sub-model\'s trained backbone (strict load) instead of the reference\'s '
+                             'strict=False load, which keeps only the head (quirk C2)')
     args = parser.parse_args(argv)
 
     with open(args.csv_file, newline='') as csvfile:
@@ -89,7 +117,8 @@ def main(argv=None):
     if not entries:
         print('No submodels found in CSV file!')
         return None
-    merged, final_class_names = merge(entries, args.submodels_folder, args.model_name)
+    merged, final_class_names = merge(entries, args.submodels_folder, args.model_name,
+                                      keep_backbone=args.keep_backbone)
     if torch.cuda.is_available():  # reference :148-151 dummy forward, on the device path
         out = merged.forward_maps(torch.zeros(2, 128, 251))
         print('Merged model output shape:', tuple(out.shape))

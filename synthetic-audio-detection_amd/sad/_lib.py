@@ -87,6 +87,11 @@ SIGNATURES = {
     'sad_backbone_run_img3': (ctypes.c_int, [P, P, I64, I64, P, P, SZ, P]),
     'sad_backbone_stem_run': (ctypes.c_int, [P, P, I64, P, P]),
     'sad_backbone_run_debug': (ctypes.c_int, [P, P, I64, P, P, P, SZ, P]),
+    # shared-trunk ensembles (include/sad.h): trunk = stem..layer3, tail = layer4 + pool
+    'sad_backbone_trunk_run': (ctypes.c_int, [P, P, P, I64, I64, P, P, SZ, P]),
+    'sad_backbone_tail_run': (ctypes.c_int, [P, P, I64, I64, P, P, SZ, P]),
+    'sad_backbone_shared_workspace_size': (ctypes.c_int, [P, I64, ctypes.POINTER(SZ)]),
+    'sad_backbone_shared_run': (ctypes.c_int, [P, FPP, I32, P, P, I64, I64, FPP, P, SZ, P]),
     'sad_resnet_plan_create': (ctypes.c_int, [FPP, I32, I32, ctypes.POINTER(I32), I32, I32, I32,
                                               ctypes.POINTER(P)]),
     'sad_resnet_plan_destroy': (ctypes.c_int, [P]),

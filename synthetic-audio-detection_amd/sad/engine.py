@@ -13,7 +13,11 @@ This is the MI355X replacement of the reference's device work:
     merge (inference_runner.py:36-48,62-73)
   * ``Engine``    -- a merged checkpoint's state dict -> the three above.
     Sub-models whose ``base.*`` tensors are identical (the reference's quirk
-    C2 makes that the normal case) share ONE backbone run.
+    C2 makes that the normal case) share ONE backbone run.  ResNet-18
+    sub-models that differ in ``layer4`` alone (trained on one frozen trunk,
+    merged with ``--keep-backbone``) run the trunk once and one layer4 tail
+    each (``Engine.features``); the deeper plans run one full backbone per
+    distinct sub-model.
 
 Every call is asynchronous on torch's current stream of the engine's device.
 """
@@ -243,6 +247,60 @@ class Backbone:
                       ws.numel(), _lib.stream_handle(self.device))
         return feats
 
+    def _input(self, x: torch.Tensor, kind: str):
+        """(map pointer, img pointer) of the trunk entries for x of `kind`."""
+        if kind not in ('maps', 'img'):
+            raise ValueError(f"kind must be 'maps' or 'img' (got {kind!r})")
+        shape = (MAP_H, MAP_W) if kind == 'maps' else (512, 512)
+        assert x.dtype == torch.float32 and x.shape[1:] == shape and x.is_contiguous() and x.device == self.device
+        return (_lib.ptr(x), None) if kind == 'maps' else (None, _lib.ptr(x))
+
+    def trunk(self, x: torch.Tensor, kind: str = 'maps') -> torch.Tensor:
+        """Stem, layer1, layer2 and layer3 on maps [B,128,251] or images
+        [B,512,512] -> layer3's output NHWC [B,32,32,256] in the plan's
+        activation layout (bf16x3: the split layout, 512 bf16 per pixel)."""
+        mp, ip = self._input(x, kind)
+        B = x.shape[0]
+        l3 = torch.empty(B, 32, 32, _act_channels(self.dtype, 256), device=self.device, dtype=self.tdtype)
+        mb = max(1, min(self.micro_batch, B))
+        ws = self.workspace(mb)
+        with torch.cuda.device(self.device):
+            _lib.call('sad_backbone_trunk_run', self._plan, mp, ip, B, mb, _lib.ptr(l3), _lib.ptr(ws), ws.numel(),
+                      _lib.stream_handle(self.device))
+        return l3
+
+    def tail(self, l3: torch.Tensor) -> torch.Tensor:
+        """layer4 + average pool on ``trunk``'s output (left intact) -> feats [B,512]."""
+        B = l3.shape[0]
+        assert l3.shape == (B, 32, 32, _act_channels(self.dtype, 256)) and l3.dtype == self.tdtype
+        assert l3.is_contiguous() and l3.device == self.device
+        feats = torch.empty(B, 512, device=self.device, dtype=torch.float32)
+        mb = max(1, min(self.micro_batch, B))
+        ws = self.workspace(mb)
+        with torch.cuda.device(self.device):
+            _lib.call('sad_backbone_tail_run', self._plan, _lib.ptr(l3), B, mb, _lib.ptr(feats), _lib.ptr(ws),
+                      ws.numel(), _lib.stream_handle(self.device))
+        return feats
+
+    def shared(self, tails: Sequence['Backbone'], x: torch.Tensor, kind: str = 'maps') -> List[torch.Tensor]:
+        """This backbone's trunk once per micro-batch chunk, then the tail of
+        every backbone in `tails` on it (sad_backbone_shared_run) -> one feats
+        [B,512] per tail.  The micro-batch is this backbone's."""
+        mp, ip = self._input(x, kind)
+        B = x.shape[0]
+        feats = [torch.empty(B, 512, device=self.device, dtype=torch.float32) for _ in tails]
+        mb = max(1, min(self.micro_batch, B))
+        sz = _lib.SZ()
+        _lib.call('sad_backbone_shared_workspace_size', self._plan, mb, _lib.ctypes.byref(sz))
+        if self._ws is None or self._ws.numel() < sz.value:
+            self._ws = torch.empty(sz.value, dtype=torch.uint8, device=self.device)
+        plans = (_lib.ctypes.c_void_p * len(tails))(*[t._plan.value for t in tails])
+        fp = (_lib.ctypes.c_void_p * len(tails))(*[f.data_ptr() for f in feats])
+        with torch.cuda.device(self.device):
+            _lib.call('sad_backbone_shared_run', self._plan, plans, len(tails), mp, ip, B, mb, fp,
+                      _lib.ptr(self._ws), self._ws.numel(), _lib.stream_handle(self.device))
+        return feats
+
     def stem(self, maps: torch.Tensor) -> torch.Tensor:
         """NHWC [B,128,128,64] in the plan dtype (bf16x3: fp32 decoded from the split layout)."""
         B = maps.shape[0]
@@ -393,6 +451,50 @@ def _digest(tensors: List[torch.Tensor]) -> str:
     return h.hexdigest()
 
 
+TAIL_PREFIX = 'layer4.'  # the part reference training changes; everything else is the trunk
+
+
+class Grouping:
+    """How an ensemble's sub-models share backbone work (``group_backbones``).
+
+    feat_index[h]    distinct backbone of sub-model h (order of first appearance)
+    first[j]         the first sub-model that uses distinct backbone j
+    trunk_of[j]      distinct trunk (stem, layer1-3) of backbone j, by first appearance
+    shared           lists of backbone indices: two or more distinct tails
+                     (layer4) on one trunk, which run the trunk once
+    """
+
+    def __init__(self, feat_index, first, trunk_of, shared):
+        self.feat_index, self.first, self.trunk_of, self.shared = feat_index, first, trunk_of, shared
+        self.n_backbones = len(first)
+        self.n_trunks = len(set(trunk_of))
+
+    def describe(self) -> str:
+        n = len(self.feat_index)
+        return f'{n} sub-model{"s" if n != 1 else ""}: {self.n_trunks} trunk{"s" if self.n_trunks != 1 else ""}, ' \
+               f'{self.n_backbones} tail{"s" if self.n_backbones != 1 else ""}'
+
+
+def group_backbones(base_sds: Sequence[Dict[str, torch.Tensor]]) -> Grouping:
+    """Group sub-model backbones (timm keys) by content, on the host.  Trunk
+    tensors (everything outside ``layer4.``) and tail tensors (``layer4.*``)
+    are hashed separately; ``num_batches_tracked`` counts for neither.  Two
+    sub-models are one backbone when both hashes agree; distinct backbones with
+    one trunk hash form a shared group."""
+    pairs, trunks, feat_index, first, trunk_of = {}, {}, [], [], []
+    for h, sd in enumerate(base_sds):
+        keys = [k for k in sorted(sd) if not k.endswith('num_batches_tracked')]
+        trunk = _digest([sd[k] for k in keys if not k.startswith(TAIL_PREFIX)])
+        tail = _digest([sd[k] for k in keys if k.startswith(TAIL_PREFIX)])
+        if (trunk, tail) not in pairs:
+            pairs[(trunk, tail)] = len(first)
+            first.append(h)
+            trunk_of.append(trunks.setdefault(trunk, len(trunks)))
+        feat_index.append(pairs[(trunk, tail)])
+    shared = [[j for j, t in enumerate(trunk_of) if t == tr] for tr in range(len(trunks))]
+    return Grouping(feat_index, first, trunk_of, [g for g in shared if len(g) >= 2])
+
+
 def split_merged_state(sd: Dict[str, torch.Tensor]):
     """merged state dict -> (sorted sub-model indices, {i: base_sd}, {i: head_sd}).
     Index parsing follows inference_runner.py:88-98 (sorted ints after
@@ -425,7 +527,7 @@ class Engine:
         if not idx:
             raise ValueError('state dict has no sub_models.<i>.* keys')
         self.indices = idx
-        digests, self.backbones, feat_index = {}, [], []
+        self.backbones = []
         archs = {_arch(bases[i]) for i in idx}
         if len(archs) != 1:
             raise ValueError(f'sub-models mix backbone architectures {sorted(archs)}')
@@ -435,23 +537,43 @@ class Engine:
             missing = [k for k in keys if not any(s.startswith(k + '.') for s in bases[i])]
             if missing:
                 raise KeyError(f'sub-model {i} lacks backbone tensors {missing[:3]}...')
-            d = _digest([bases[i][k] for k in sorted(bases[i]) if not k.endswith('num_batches_tracked')])
-            if d not in digests:
-                digests[d] = len(self.backbones)
-                if self.arch == 'resnet18':  # the tuned ResNet-18 plan
-                    self.backbones.append(Backbone(bases[i], self.device, dtype, micro_batch))
-                else:
-                    self.backbones.append(ResNetBackbone(bases[i], self.arch, self.device, dtype, micro_batch))
-            feat_index.append(digests[d])
+        # one plan per distinct full backbone (trunk + tail), each usable alone
+        self.grouping = group_backbones([bases[i] for i in idx])
+        for h in self.grouping.first:
+            if self.arch == 'resnet18':  # the tuned ResNet-18 plan
+                self.backbones.append(Backbone(bases[idx[h]], self.device, dtype, micro_batch))
+            else:
+                self.backbones.append(ResNetBackbone(bases[idx[h]], self.arch, self.device, dtype, micro_batch))
+        # distinct tails on one trunk run the trunk once (the tuned ResNet-18
+        # plan only: the deeper plans run one full backbone per distinct sub-model)
+        self.shared_groups = self.grouping.shared if self.arch == 'resnet18' else []
         self.num_features = arch_spec(self.arch)[2]
-        self.heads = Heads([heads[i] for i in idx], feat_index, len(self.backbones), self.device,
+        self.heads = Heads([heads[i] for i in idx], self.grouping.feat_index, len(self.backbones), self.device,
                            feat_dim=self.num_features)
         self.frontend = FrontEnd(self.device, norm=norm)
         self.n_heads = len(idx)
 
+    def features(self, x: torch.Tensor, kind: str = 'maps') -> List[torch.Tensor]:
+        """Pooled features of every distinct backbone, aligned with
+        ``self.backbones``: x is maps [B,128,251] (kind='maps') or one-channel
+        images [B,512,512] (kind='img').  Backbones of a shared group run their
+        trunk once per micro-batch chunk (the micro-batch of the group's first
+        backbone); the values equal ``bb(x)`` / ``bb.forward_images(x)`` bit
+        for bit."""
+        if kind not in ('maps', 'img'):
+            raise ValueError(f"kind must be 'maps' or 'img' (got {kind!r})")
+        feats: List[torch.Tensor | None] = [None] * len(self.backbones)
+        for group in self.shared_groups:
+            bbs = [self.backbones[j] for j in group]
+            for j, f in zip(group, bbs[0].shared(bbs, x, kind)):
+                feats[j] = f
+        for j, bb in enumerate(self.backbones):
+            if feats[j] is None:
+                feats[j] = bb(x) if kind == 'maps' else bb.forward_images(x)
+        return feats
+
     def forward_maps(self, maps: torch.Tensor):
-        feats = [bb(maps) for bb in self.backbones]
-        return self.heads(feats)
+        return self.heads(self.features(maps))
 
     def forward_pcm(self, pcm: torch.Tensor):
         return self.forward_maps(self.frontend(pcm))

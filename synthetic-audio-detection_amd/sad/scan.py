@@ -367,7 +367,7 @@ class Scanner:
         for s in range(0, n_kept, bs):
             e = min(s + bs, n_kept)
             m = eng.frontend.windows(pack.arena, pack.offsets[s:e], out=maps[:e - s])
-            eng.heads([bb(m) for bb in eng.backbones], logits=per_head[:e - s], merged=logits[s:e])
+            eng.heads(eng.features(m), logits=per_head[:e - s], merged=logits[s:e])
         pack.events[5].record()
         _, label, mean = postprocess(logits, pack.row_start, self.threshold, self.smooth)
         pack.h_offsets = torch.empty(n_kept, dtype=torch.int64, pin_memory=True)

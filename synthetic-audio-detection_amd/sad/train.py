@@ -754,6 +754,67 @@ class MixedNet(TrainNet):
         return ResNetBackbone(self.base_state_dict(), self.model_name, self.device, 'bf16x3', micro_batch)
 
 
+TRUNK_PREFIXES = ('conv1.', 'bn1.', 'layer1.', 'layer2.', 'layer3.')
+
+
+def trunk_keys(base_sd) -> List[str]:
+    """The state-dict keys of the frozen trunk (conv1, bn1, layer1-3: parameters
+    and BN buffers, counters included) -- everything outside layer4."""
+    return [k for k in base_sd if k.startswith(TRUNK_PREFIXES)]
+
+
+class FrozenTrunkNet(TrainNet):
+    """``--trunk CHECKPOINT``: resnet18 with conv1, bn1 and layer1-3 taken from a
+    trained checkpoint and run in eval mode for the whole run, layer4 (and the
+    head) trained as usual.
+
+    The trunk's running statistics normalise and nothing in it is updated, so
+    every sub-model trained on one CHECKPOINT keeps that trunk bit for bit and
+    the merged ensemble runs it once (``Engine.features``).  Eval-mode BN folds
+    into the convs, so the trunk is the inference plan's
+    ``sad_backbone_trunk_run`` on fp32 images; its layer3 activation (NHWC, the
+    compute dtype) enters the train-mode layer4 blocks where ``MixedNet`` hands
+    over.  There is no backward below layer4 (``unfreeze_layer3`` is skipped:
+    the reference never steps layer3 anyway, quirk C4)."""
+
+    frozen_trunk = True
+
+    def __init__(self, base_sd, head_sd, trunk_sd, device='cuda', dtype: str = 'bf16', model_name: str = 'resnet18',
+                 head_loss: bool = False, micro_batch: int = 32):
+        if model_name != 'resnet18' or dtype not in ('bf16', 'fp32'):
+            raise ValueError('a frozen trunk needs resnet18 in bf16 or fp32 '
+                             f'(got {model_name}, {dtype}): the trunk runs on the tuned ResNet-18 inference plan')
+        base = OrderedDict(base_sd)
+        keys = trunk_keys(base)
+        missing = [k for k in keys if k not in trunk_sd]
+        if missing:
+            raise KeyError(f'trunk checkpoint lacks {len(missing)} tensors (e.g. {missing[0]})')
+        for k in keys:
+            t = torch.as_tensor(trunk_sd[k])
+            if tuple(t.shape) != tuple(base[k].shape):
+                raise ValueError(f'trunk tensor {k!r} has shape {tuple(t.shape)}, expected {tuple(base[k].shape)}')
+            base[k] = t.detach().cpu().clone()
+        super().__init__(base, head_sd, device, dtype, model_name, head_loss)
+        self.trunk_micro_batch = micro_batch
+        self._trunk_plan = None
+
+    def invalidate_packed(self):
+        super().invalidate_packed()
+        self._trunk_plan = None  # the parameters were overwritten (a resumed checkpoint)
+
+    def trunk_plan(self) -> Backbone:
+        if self._trunk_plan is None:
+            self._trunk_plan = Backbone(self.base_state_dict(), self.device, self.dtype, self.trunk_micro_batch)
+        return self._trunk_plan
+
+    def forward_train(self, img: torch.Tensor, keep_from: int = 4, stem_chunk: int = 16):
+        """img [B, 512, 512] fp32 -> (pooled features fp32, saved layer4 activations)."""
+        saved = {}
+        a = self.trunk_plan().trunk(img, 'img')
+        a = self.blocks_fwd(a, [b for b in self.blocks if b[0].startswith('layer4')], saved, 4)
+        return self.pool(a), saved
+
+
 def ce_loss(feats: torch.Tensor, targets: torch.Tensor, scale: float = 0.0, want_grad: bool = False,
             want_pred: bool = False):
     """(dlogits or None, device [loss_sum, n_correct][, argmax int32 [B]]) of
@@ -776,12 +837,18 @@ class Trainer:
     accumulator, with an optional process group (DDP over RCCL)."""
 
     def __init__(self, base_sd, head_sd, device='cuda', dtype: str = 'bf16', lr: float = 1e-3, group=None,
-                 world: int = 1, model_name: str = 'resnet18', head_loss: bool = False, seed: int = 42):
+                 world: int = 1, model_name: str = 'resnet18', head_loss: bool = False, seed: int = 42,
+                 trunk_sd: Dict[str, torch.Tensor] | None = None):
         """head_loss: CrossEntropy on model.head's two logits (train-mode head,
         trained with layer4) instead of the reference's pooled features (quirk
-        C1, the default)."""
-        self.net = (MixedNet(base_sd, head_sd, device, model_name, head_loss) if dtype == 'mixed'
-                    else TrainNet(base_sd, head_sd, device, dtype, model_name, head_loss))
+        C1, the default).  trunk_sd (``--trunk``): a trained checkpoint's state
+        dict whose conv1, bn1 and layer1-3 replace the initial ones and stay
+        frozen in eval mode (``FrozenTrunkNet``; images must then be fp32)."""
+        if trunk_sd is not None:
+            self.net = FrozenTrunkNet(base_sd, head_sd, trunk_sd, device, dtype, model_name, head_loss)
+        else:
+            self.net = (MixedNet(base_sd, head_sd, device, model_name, head_loss) if dtype == 'mixed'
+                        else TrainNet(base_sd, head_sd, device, dtype, model_name, head_loss))
         self.head_loss = head_loss
         rank = 0
         if world > 1:
@@ -815,8 +882,11 @@ class Trainer:
 
     # reference: for p in layer3.parameters(): p.requires_grad = True  (:687-691)
     def unfreeze_layer3(self):
+        """Returns False when there is nothing to unfreeze (a frozen trunk)."""
+        if getattr(self.net, 'frozen_trunk', False):
+            return False  # layer3 runs folded in eval mode: no gradient exists below layer4
         if self.layer3_unfrozen:
-            return
+            return True
         self.layer3_unfrozen = True
         a3, b3 = self.net.range3
         self.net.gflat[a3:b3].zero_()
@@ -826,6 +896,7 @@ class Trainer:
             if n.startswith('layer3.'):
                 lo, hi = self.net.offsets[n]
                 self.grads3[n] = self._g3flat[lo - a3:hi - a3].view(self.net.params[n].shape)
+        return True
 
     @property
     def current_lr(self) -> float:

@@ -30,15 +30,20 @@ Differences (documented in DESIGN.md / INTEGRATION.md):
   * ``--num_gpus > 1`` = one process per GPU (torchrun) over RCCL instead of
     DataParallel threads: each rank loads ``--batch-size`` files per step;
     per-replica BN statistics as in DP; gradients all-reduced.
-  * no CPU fallback; ``--model-name`` must be a BasicBlock ResNet (resnet18,
-    resnet34): the device backward kernels implement timm's BasicBlock.
+  * no CPU fallback; ``--model-name`` must be resnet18 / resnet34 (timm's
+    BasicBlock) or resnet50 / resnet101 / resnet152 (Bottleneck): the device
+    forward and backward implement those two block types.
   * extra flags: ``--precision {bf16,mixed,fp32}`` (default bf16 = throughput
     mode; mixed = the frozen stem/layers 1-3 in fp32 and layer4 in bf16, whose
     layer4 gradients track fp32 autograd to cosine >= 0.95),
     ``--max-steps`` (stop an epoch early; benchmarking), ``--head-loss``
     (CrossEntropy and accuracy through model.head, trained with layer4: the
     BinaryClassifier the merger and inference use; off by default, so C1 is
-    reproduced unless asked for).
+    reproduced unless asked for), ``--trunk CHECKPOINT`` (resnet18, bf16 or
+    fp32: conv1, bn1 and layer1-3 come from CHECKPOINT and run frozen in eval
+    mode on the inference plan's trunk entry; sub-models trained on one trunk
+    and merged with ``model_merger.py --keep-backbone`` run it once at
+    inference).
   * TensorBoard is optional (not installed here): scalars are logged instead.
 """
 from __future__ import annotations
@@ -66,7 +71,8 @@ warnings.filterwarnings("ignore")
 
 SEGMENT_LENGTH = 4 * 32000
 # timm.list_models('resnet*') is unavailable offline: the choices the reference's
-# CLI accepts for --model-name (timm 0.9 names); resnet18 / resnet34 run on the device.
+# CLI accepts for --model-name (timm 0.9 names); resnet18 / resnet34 (BasicBlock) and
+# resnet50 / resnet101 / resnet152 (Bottleneck) train on the device (sad.weights.ARCHS).
 RESNET_MODELS = ['resnet10t', 'resnet14t', 'resnet18', 'resnet18d', 'resnet26', 'resnet26d', 'resnet26t',
                  'resnet32ts', 'resnet33ts', 'resnet34', 'resnet34d', 'resnet50', 'resnet50_gn', 'resnet50d',
                  'resnet50t', 'resnet51q', 'resnet61q', 'resnet101', 'resnet101d', 'resnet152', 'resnet152d',
@@ -99,7 +105,19 @@ def parse_args(argv=None):
                         help='train through model.head: CrossEntropy and accuracy on the BinaryClassifier head\'s two '
                              'logits (train-mode BN + dropout), the head trained with layer4.  Default off: the '
                              'reference computes them on the 512 pooled features and never calls the head (quirk C1)')
-    return parser.parse_args(argv)
+    parser.add_argument('--trunk', default='', type=str, metavar='CHECKPOINT',
+                        help='trainer checkpoint whose conv1, bn1 and layer1-3 (parameters and BN statistics) are '
+                             'loaded after the seeded init and stay frozen in eval mode; layer4 and the head train as '
+                             'usual.  resnet18 with --precision bf16 or fp32 only')
+    args = parser.parse_args(argv)
+    if args.trunk:
+        if args.model_name != 'resnet18':
+            parser.error(f'--trunk needs --model-name resnet18 (got {args.model_name}): the frozen trunk runs on '
+                         'the tuned ResNet-18 inference plan')
+        if args.precision not in ('bf16', 'fp32'):
+            parser.error(f'--trunk needs --precision bf16 or fp32 (got {args.precision}): the frozen trunk runs in '
+                         'the precision of layer4')
+    return args
 
 
 def setup_logging():
@@ -486,9 +504,15 @@ def main(argv=None):
     from sad import train as st
     logging.info("Creating model with RANDOM weights...")
     base_sd, head_sd = st.init_state_dict(args.seed, args.model_name)
+    trunk_sd = None
+    if getattr(args, 'trunk', ''):
+        logging.info(f"Loading the frozen trunk (conv1, bn1, layer1-3) from '{args.trunk}'")
+        trunk_sd = torch.load(args.trunk, map_location='cpu', weights_only=True)['state_dict']
     trainer = st.Trainer(base_sd, head_sd, device, args.precision, lr=args.lr, group=group, world=world,
-                         model_name=args.model_name, head_loss=getattr(args, 'head_loss', False), seed=args.seed)
-    frontend = st.TrainFrontEnd(device, args.precision)
+                         model_name=args.model_name, head_loss=getattr(args, 'head_loss', False), seed=args.seed,
+                         trunk_sd=trunk_sd)
+    # the frozen trunk is the inference plan's: it reads fp32 images
+    frontend = st.TrainFrontEnd(device, 'fp32' if trunk_sd is not None else args.precision)
     model = DeviceModel(trainer, frontend, rank, world, group)
 
     train_loader, val_loader = get_dataloaders(args, rank, world)
@@ -519,7 +543,8 @@ def main(argv=None):
         logging.info(f'\nEpoch: {epoch}/{args.epochs - 1}')
         if epoch == args.epochs // 3:
             logging.info("Unfreezing more layers...")
-            trainer.unfreeze_layer3()
+            if trainer.unfreeze_layer3() is False:
+                logging.info("Skipped: layer3 belongs to the frozen trunk (--trunk)")
         if world > 1 and hasattr(train_loader.sampler, 'set_epoch'):
             train_loader.sampler.set_epoch(epoch)
         train_loss, train_acc, total_steps = train(args, train_loader, model, None, optimizer, scheduler, epoch,
