@@ -248,7 +248,11 @@ typedef struct sad_backbone_plan sad_backbone_plan;
  * Order: conv1/bn1, then for layer1..4, block 0..1: conv1/bn1, conv2/bn2,
  * [downsample.0/downsample.1 for block 0 of layer2..4].  n_params must be
  * 5 * 20 = 100.  BN is folded (eps 1e-5) and weights are re-laid out
- * [Cout][KH][KW][Cin] in `dtype` on the current device. */
+ * [Cout][KH][KW][Cin] in `dtype` on the current device.
+ * map_h, map_w: 1..512 each.  The stem's in-kernel resize is the plain bilinear
+ * filter (UPSAMPLING ONLY: what torchvision's antialiased Resize((512,512))
+ * reduces to when it enlarges); a side above 512 would be point-sampled, so it
+ * is refused with SAD_ERR_ARG before any allocation (*out untouched). */
 int sad_backbone_plan_create(const float* const* params, int32_t n_params, int32_t dtype,
                              int32_t map_h, int32_t map_w, sad_backbone_plan** out);
 int sad_backbone_plan_destroy(sad_backbone_plan* plan);
@@ -273,9 +277,18 @@ int sad_backbone_run_img3(const sad_backbone_plan* plan, const float* img3, int6
                           int64_t micro_batch, float* feats, void* workspace, size_t ws_bytes,
                           void* stream);
 /* Debug/parity entry: run only the fused resize+stem (conv1+bn1+relu+maxpool)
- * on B maps, writing NHWC [B,128,128,64] in the plan's dtype. */
+ * on B maps, writing NHWC [B,128,128,64] in the plan's dtype (SAD_BF16X3: 128
+ * bf16 per pixel, [hi 32 | lo 32] per 32 channels).  The maps are the plan's
+ * map_h x map_w, both <= 512: the resize is upsampling only, no antialias.
+ * B <= 65535; B = 0 launches nothing. */
 int sad_backbone_stem_run(const sad_backbone_plan* plan, const float* map, int64_t B,
                           void* out, void* stream);
+/* Debug/parity entry: the same fused stem on already resized images, exactly
+ * one of img [B,512,512] (the folded stems of sad_backbone_run_img) and img3
+ * [B,3,512,512] (the distinct-channel stem of sad_backbone_run_img3) non-null;
+ * out as above. */
+int sad_backbone_stem_run_img(const sad_backbone_plan* plan, const float* img, const float* img3,
+                              int64_t B, void* out, void* stream);
 /* Debug/parity entry: layer4 output NHWC [B,16,16,512] (plan dtype) for B <=
  * micro_batch, in addition to the pooled features. */
 int sad_backbone_run_debug(const sad_backbone_plan* plan, const float* map, int64_t B,
@@ -332,7 +345,10 @@ int sad_backbone_shared_run(const sad_backbone_plan* trunk_plan,
  * state-dict order (conv1/bn1 first; per block its convs, then
  * downsample.0/downsample.1 where present).  dtype SAD_BF16X3 with
  * SAD_BOTTLENECK runs every conv with the fourth split product W_lo.X_lo too
- * (|dlogit| <= 1e-3 on resnet50; environment SAD_DEEP_X4=0: three products). */
+ * (|dlogit| <= 1e-3 on resnet50; environment SAD_DEEP_X4=0: three products).
+ * map_h, map_w: 1..512 each, as sad_backbone_plan_create (the stem's resize is
+ * upsampling only, no antialias; a larger side is refused with SAD_ERR_ARG
+ * before any allocation, *out untouched). */
 #define SAD_BASIC_BLOCK 0
 #define SAD_BOTTLENECK 1
 typedef struct sad_resnet_plan sad_resnet_plan;
@@ -353,6 +369,12 @@ int sad_resnet_run_img(const sad_resnet_plan* plan, const float* img, int64_t B,
 /* same from [B, 3, 512, 512] fp32 images with possibly distinct channels */
 int sad_resnet_run_img3(const sad_resnet_plan* plan, const float* img3, int64_t B, int64_t micro_batch,
                         float* feats, void* workspace, size_t ws_bytes, void* stream);
+/* Debug/parity entry: only this plan's stem (with its fourth split product
+ * where the plan carries it), exactly one of map [B,map_h,map_w], img
+ * [B,512,512] and img3 [B,3,512,512] non-null; out: NHWC [B,128,128,64] in the
+ * plan's dtype, laid out as sad_backbone_stem_run's. */
+int sad_resnet_stem_run(const sad_resnet_plan* plan, const float* map, const float* img,
+                        const float* img3, int64_t B, void* out, void* stream);
 
 /* Kernel-level timing of the backbone's block-conv launches (bench.py's
  * roofline of the dominant kernel): between begin and end, every block-conv

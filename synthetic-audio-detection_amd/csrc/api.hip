@@ -180,6 +180,15 @@ int fold_stem(const float* const* params, int dtype, void** w_out, float** b_out
   }
   return upload((void**)b_out, b);
 }
+
+int check_map_upsamples(int map_h, int map_w) {
+  if (map_h > 512 || map_w > 512) {
+    set_error("argument check failed: map shape " + std::to_string(map_h) + " x " + std::to_string(map_w) +
+              " exceeds the limit of 512 per side (the stem's resize is upsampling only: no antialias filter)");
+    return SAD_ERR_ARG;
+  }
+  return SAD_OK;
+}
 }  // namespace sad
 
 extern "C" int sad_backbone_plan_create(const float* const* params, int32_t n_params, int32_t dtype,
@@ -189,6 +198,7 @@ extern "C" int sad_backbone_plan_create(const float* const* params, int32_t n_pa
   SAD_REQUIRE(n_params == (int)specs.size() * 5, "n_params must be 100 (20 conv+BN groups)");
   SAD_REQUIRE(dtype == SAD_F32 || dtype == SAD_BF16 || dtype == SAD_BF16X3, "dtype");
   SAD_REQUIRE(map_h > 0 && map_w > 0, "map shape");
+  if (int rc = check_map_upsamples(map_h, map_w)) return rc;
   for (int i = 0; i < n_params; ++i) SAD_REQUIRE(params[i] != nullptr, "null parameter pointer");
   auto* p = new sad_backbone_plan();
   p->dtype = dtype;
@@ -197,7 +207,10 @@ extern "C" int sad_backbone_plan_create(const float* const* params, int32_t n_pa
   (void)hipGetDevice(&p->device);
   std::vector<double> sc, sh;
   int rc;
-  if ((rc = fold_stem(params, dtype, &p->stem_w, &p->stem_b, &p->stem_w3))) return rc;
+  if ((rc = fold_stem(params, dtype, &p->stem_w, &p->stem_b, &p->stem_w3))) {
+    sad_backbone_plan_destroy(p);  // (no device: the first upload fails)
+    return rc;
+  }
   // first-generation per-conv weights (SAD_BACKBONE_PATH=igemm; fp32 / bf16 only)
   for (size_t ci = 1; ci < specs.size() && dtype != SAD_BF16X3; ++ci) {
     const ConvSpec& s = specs[ci];
@@ -869,6 +882,14 @@ extern "C" int sad_backbone_stem_run(const sad_backbone_plan* p, const float* ma
                                      void* stream) {
   SAD_REQUIRE(p && map && out && B >= 0, "null args");
   StemArgs st{map, nullptr, p->mh, p->mw, p->stem_w, p->stem_b, out, B};
+  return launch_stem(st, p->dtype, (hipStream_t)stream);
+}
+
+extern "C" int sad_backbone_stem_run_img(const sad_backbone_plan* p, const float* img, const float* img3, int64_t B,
+                                         void* out, void* stream) {
+  SAD_REQUIRE(p && out && B >= 0, "null args");
+  SAD_REQUIRE((img != nullptr) != (img3 != nullptr), "exactly one of img / img3");
+  StemArgs st{nullptr, img, p->mh, p->mw, p->stem_w, p->stem_b, out, B, img3, p->stem_w3};
   return launch_stem(st, p->dtype, (hipStream_t)stream);
 }
 

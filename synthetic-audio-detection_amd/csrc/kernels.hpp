@@ -154,5 +154,9 @@ int upload_typed(void** dst, const std::vector<double>& v, int dtype, int64_t ro
 // timm conv1 + bn1 (5 arrays) -> the stem kernel's weight layout and bias, and
 // (w3_out) the per-channel fp32 weights of the 3-distinct-channel stem
 int fold_stem(const float* const* params, int dtype, void** w_out, float** b_out, float** w3_out);
+// The stems' in-kernel resize is a plain bilinear sample: right for an upsample
+// only (a side above 512 would be point-sampled where the reference's
+// Resize((512,512)) applies its antialias filter).  SAD_ERR_ARG for such a map.
+int check_map_upsamples(int map_h, int map_w);
 
 }  // namespace sad

@@ -134,6 +134,7 @@ extern "C" int sad_resnet_plan_create(const float* const* params, int32_t n_para
   SAD_REQUIRE(block == SAD_BASIC_BLOCK || block == SAD_BOTTLENECK, "block must be SAD_BASIC_BLOCK or SAD_BOTTLENECK");
   SAD_REQUIRE(dtype == SAD_F32 || dtype == SAD_BF16 || dtype == SAD_BF16X3, "dtype");
   SAD_REQUIRE(map_h > 0 && map_w > 0, "map shape");
+  if (int rc = check_map_upsamples(map_h, map_w)) return rc;
   const int exp = block == SAD_BOTTLENECK ? 4 : 1;
   const int per_block = block == SAD_BOTTLENECK ? 3 : 2;
   int need = 1, inp = 64;
@@ -347,6 +348,15 @@ static int rn_run(const sad_resnet_plan* p, const float* map, const float* img, 
     if (rc) return rc;
   }
   return SAD_OK;
+}
+
+extern "C" int sad_resnet_stem_run(const sad_resnet_plan* p, const float* map, const float* img, const float* img3,
+                                   int64_t B, void* out, void* stream) {
+  SAD_REQUIRE(p && out && B >= 0, "null args");
+  SAD_REQUIRE((map != nullptr) + (img != nullptr) + (img3 != nullptr) == 1, "exactly one of map / img / img3");
+  StemArgs st{map, img, p->mh, p->mw, p->stem_w, p->stem_b, out, B, img3, p->stem_w3};
+  st.x4 = p->x4;
+  return launch_stem(st, p->dtype, (hipStream_t)stream);
 }
 
 extern "C" int sad_resnet_run(const sad_resnet_plan* p, const float* map, int64_t B, int64_t mb, float* feats,

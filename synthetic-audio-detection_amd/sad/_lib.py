@@ -86,6 +86,7 @@ SIGNATURES = {
     'sad_backbone_run_img': (ctypes.c_int, [P, P, I64, I64, P, P, SZ, P]),
     'sad_backbone_run_img3': (ctypes.c_int, [P, P, I64, I64, P, P, SZ, P]),
     'sad_backbone_stem_run': (ctypes.c_int, [P, P, I64, P, P]),
+    'sad_backbone_stem_run_img': (ctypes.c_int, [P, P, P, I64, P, P]),
     'sad_backbone_run_debug': (ctypes.c_int, [P, P, I64, P, P, P, SZ, P]),
     # shared-trunk ensembles (include/sad.h): trunk = stem..layer3, tail = layer4 + pool
     'sad_backbone_trunk_run': (ctypes.c_int, [P, P, P, I64, I64, P, P, SZ, P]),
@@ -100,6 +101,7 @@ SIGNATURES = {
     'sad_resnet_run': (ctypes.c_int, [P, P, I64, I64, P, P, SZ, P]),
     'sad_resnet_run_img': (ctypes.c_int, [P, P, I64, I64, P, P, SZ, P]),
     'sad_resnet_run_img3': (ctypes.c_int, [P, P, I64, I64, P, P, SZ, P]),
+    'sad_resnet_stem_run': (ctypes.c_int, [P, P, P, P, I64, P, P]),
     'sad_profile_begin': (ctypes.c_int, []),
     'sad_profile_end': (ctypes.c_int, [I32, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(I64),
                                        ctypes.POINTER(ctypes.c_double)]),
