@@ -31,9 +31,10 @@
 // 0, 1 (3 more fragments).  At 8 tiles per strip (128 x 128 maps) conv1 runs
 // 1.15x its halo-free MFMA work (21 fragments: 1.31x).
 //
-// LDS (142 KB): 2 x input patch [20 x 20 pixels][128 B] (the next tile's patch
+// LDS (154 KB): 2 x input patch [20 x 20 pixels][128 B] (the next tile's patch
 // is DMA'd during this tile's conv1, one piece per 5 units), the intermediate
-// [18 rows][18 x 128 B + 16 B pad] and the biases.  Swizzles (16-B chunk c of a
+// [18 rows][18 x 128 B + 16 B pad], the biases and the waves' patch-piece
+// tables (13 KB, written once per launch).  Swizzles (16-B chunk c of a
 // pixel):
 //  * intermediate pixel (y, x): position c ^ key(x) -- a column key that is
 //    conflict-free for row-aligned fragment reads at every tap column (conv2's
@@ -49,6 +50,14 @@
 // Zero padding: patch pixels outside the image are DMA'd as zeros (offset
 // past num_records); intermediate pixels outside the image are written as 0
 // (conv2 pads the block's intermediate, not relu(b1)).
+//
+// With one wave per SIMD nothing hides behind a partner wave, so the tile loop
+// keeps what is not the convolution out of its way: the timing ablations are a
+// second kernel; the tile origin is stepped, not divided out of the tile
+// index; a lane's fragment, store and residual addresses are formed once per
+// launch and kept in registers (at most one XOR in front of a read, the rest
+// is the instruction's immediate offset); a patch piece is one table read,
+// 4 VALU and one SALU.
 #include "common.hpp"
 #include "igemm.hpp"
 #include "kernels.hpp"
@@ -75,11 +84,12 @@ constexpr int PATCH = PR * 128;            // 51,200 B
 constexpr int PROW = PWD * 128, IROW = IWD * 128 + 16;
 constexpr int OFF_I = 2 * PATCH;           // patches double-buffered
 constexpr int OFF_B = OFF_I + IWD * IROW;  // b1 [64], b2 [64] fp32
-constexpr int SMEM = OFF_B + 2 * 64 * 4;
+constexpr int OFF_T = OFF_B + 2 * 64 * 4;   // the waves' patch-piece tables: [wave][piece k][lane] int
 constexpr int NDP = PR / 8;                // 50 DMA pieces of 8 pixel rows
 constexpr int QP = (NDP + NW - 1) / NW;    // 13 per wave (waves 2, 3: 12)
 constexpr int NA = 8;                      // row-aligned conv1 fragments per wave (rows 2 + 8 pg + k)
 constexpr int NF = NA + 1;                 // + 1 leftover fragment (columns 16, 17 of those rows)
+constexpr int SMEM = OFF_T + NW * QP * 256;
 constexpr int QSKIP = 10;                  // pieces 0-9 = patch rows 0-3: a continuation tile needs no
                                            // rows 0, 1 and copies rows 2, 3 from the previous patch
 constexpr int NS = 18;                     // K-steps per conv: 9 taps x 2 halves of 32 channels
@@ -96,6 +106,7 @@ constexpr int BAD = 0x7FFFFFF0;
 // 2-way (the ds_write_b64 minimum for 128-B pixels; variant 30's key: 4-way)
 constexpr uint64_t KEY = 0xf9afad91a240ull;
 static_assert(SMEM <= 160 * 1024, "LDS budget");
+static_assert(PATCH % 128 == 0 && OFF_I % 128 == 0, "buffer offsets commute with the chunk XORs");
 static_assert(NDP % 2 == 0, "pieces");
 // conv1 unit u -> (K-step, fragment): phase A K-step-outer, phase B fragment-outer
 constexpr int l1b_s1(int u) { return u < SA * NF ? u / NF : SA + (u - SA * NF) % NB1; }
@@ -103,17 +114,51 @@ constexpr int l1b_k1(int u) { return u < SA * NF ? u % NF : (u - SA * NF) / NB1;
 }  // namespace l1b
 
 __device__ __forceinline__ int l1b_key(int x) { return (int)((l1b::KEY >> (3 * x)) & 7); }
+// LDS access by byte address (the lane constants below carry the LDS base, so
+// no base is added in front of a read; a constant added to `ad` becomes the
+// instruction's immediate offset)
+// T: a native vector type (l1b_v4, l1b_v2, f32x4) -- HIP's uint4 / uint2 are
+// structs, which the optimiser takes apart into 4-B accesses
+template <typename T>
+__device__ __forceinline__ T l1b_ld(int ad) {
+  return *(const __attribute__((address_space(3))) T*)(unsigned)ad;
+}
+template <typename T>
+__device__ __forceinline__ void l1b_st(int ad, const T& v) {
+  *(__attribute__((address_space(3))) T*)(unsigned)ad = v;
+}
 
-__global__ __launch_bounds__(256, 1) void l1block_kernel(L1BlockArgs a) {
+// One LDS-DMA piece (16 B per lane from buffer offset voff to LDS [dst + OFF +
+// 16 lane]) with M0 formed in the statement as a scalar base plus an
+// immediate, and the descriptor passed as one 128-bit scalar value.
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Winline-asm"
+template <int OFF>
+__device__ __forceinline__ void l1b_dma16(const l1b_v4& rsrc, int voff, unsigned dst) {
+  asm volatile(
+      "s_add_u32 m0, %1, %3\n\t"
+      "s_nop 0\n\t"
+      "buffer_load_dwordx4 %0, %2, 0 offen lds"
+      :
+      : "v"(voff), "s"(dst), "s"(rsrc), "n"(OFF)
+      : "memory", "m0", "scc");
+}
+#pragma clang diagnostic pop
+
+// AB: false = the production kernel, which holds no ablation code at all; true
+// = the timing-ablation form, which tests a.ablate at run time around the
+// patch DMA and the stores (launch_l1block picks it when ablate != 0).
+template <bool AB>
+__device__ __forceinline__ void l1block_body(const L1BlockArgs& a) {
   using namespace l1b;
-  extern __shared__ __attribute__((aligned(16))) char smem[];
+  extern __shared__ __attribute__((aligned(128))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int fr = lane & 15, fg = lane >> 4;
   const int cg = wave & 1, pg = wave >> 1;
   // timing ablations (wrong results; tools/l1bench.py --ablate): 1 no next-tile
   // patch DMA, 2 no intermediate stores, 4 no output stores
-  const int ab = a.ablate;
+  const int ab = AB ? a.ablate : 0;
   const int cw = cg * 32;  // this wave's first channel (both convs)
   const int w = xcd_remap(blockIdx.x, gridDim.x);
   const int tiles_y = a.H / 16, tiles_img = (a.W / 16) * tiles_y;
@@ -121,30 +166,49 @@ __global__ __launch_bounds__(256, 1) void l1block_kernel(L1BlockArgs a) {
   const int tp_begin = (int)((int64_t)w * tiles_p / gridDim.x), tp_end = (int)((int64_t)(w + 1) * tiles_p / gridDim.x);
   if (tp_begin >= tp_end) return;  // whole workgroup (uniform)
 
-  const __amdgpu_buffer_rsrc_t rx =
-      __builtin_amdgcn_make_buffer_rsrc((void*)a.x, (short)0, (int)a.x_bytes, 0x00020000);
+  // the input's buffer descriptor (base, stride 0, num_records = the image
+  // range's bytes, raw 32-bit data format), made opaque as one value: it then
+  // stays in four aligned SGPRs for the launch instead of being put together
+  // from its words in front of every piece
+  l1b_v4 rx = {(unsigned)(uintptr_t)a.x, (unsigned)((uintptr_t)a.x >> 32) & 0xFFFFu, (unsigned)a.x_bytes, 0x00020000u};
+  asm volatile("" : "+s"(rx));
   const __amdgpu_buffer_rsrc_t ro =
       __builtin_amdgcn_make_buffer_rsrc((void*)a.out, (short)0, (int)a.x_bytes, 0x00020000);
   const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
 
-  // ---- patch piece k of this wave (q = wave + 4k: rows 8q .. 8q+7): the
-  // lane's patch pixel (Y, X) and its source offset from the tile origin are
-  // tile-independent (computed once)
-  int DREL[QP], DYX[QP];
-#pragma unroll
-  for (int k = 0; k < QP; ++k) {
+  // ---- patch piece k of this wave (q = wave + 4k) covers patch slots 8q ..
+  // 8q + 7; a lane's slot r = 8q + lane / 8 is patch pixel (Y, X) = (r / 20,
+  // r % 20).  What a lane needs of its slot never changes during a launch, so
+  // it is tabled in LDS, once (as variant 31's piece table; held in 26 VGPRs it
+  // left no room to keep the fragment addresses below in registers).  An entry:
+  // bits 0-27 the source offset from the tile's first patch pixel with the
+  // swizzled chunk folded in, in 16-B units; bits 28-31 the patch edges the
+  // slot lies on -- rows 0, 1 / rows 18, 19 / columns 0, 1 / columns 18, 19:
+  // a slot on an edge that the tile shares with the image loads zeros.
+  int* const tab = (int*)(smem + OFF_T) + wave * (QP * 64) + lane;  // piece k at tab[64 k]
+  auto piece_entry = [&](int k) __attribute__((always_inline)) {
     const int r = 8 * (wave + NW * k) + (lane >> 3);
     const int Y = (r * 205) >> 12, X = r - 20 * Y;  // r / 20 exactly for r < 400
     const int c = (lane & 7) ^ l1b_key(X) ^ ((Y & 3) << 1);
-    DREL[k] = ((Y - 2) * a.W + (X - 2)) * 128 + (c << 4);
-    DYX[k] = Y | (X << 16);
-  }
+    const int edge = (Y < 2 ? 1 : 0) | (Y >= PWD - 2 ? 2 : 0) | (X < 2 ? 4 : 0) | (X >= PWD - 2 ? 8 : 0);
+    return (int)((unsigned)edge << 28) | ((Y * a.W + X) * 8 + c);
+  };
   // tile t's origin: image byte offset, (oy0, ox0), interior flag (uniform)
   struct TileO {
     int base, oy0, ox0;
   };
+  // the uniform part of a tile's pieces: the offset of its first patch pixel
+  // (2 rows up, 2 pixels left of its origin) and the edges it shares with the image
+  auto patch_base = [&](const TileO& o) __attribute__((always_inline)) { return o.base - (2 * a.W + 2) * 128; };
+  auto patch_mask = [&](const TileO& o) __attribute__((always_inline)) {
+    return (int)((unsigned)((o.oy0 == 0 ? 1 : 0) | (o.oy0 + 16 == a.H ? 2 : 0) | (o.ox0 == 0 ? 4 : 0) |
+                            (o.ox0 + 16 == a.W ? 8 : 0))
+                 << 28);
+  };
   // tiles run down column strips (ty fastest), so a tile's top halo is the
-  // previous tile's bottom rows
+  // previous tile's bottom rows.  Decoded by division once, for the
+  // workgroup's first tile; the tile loop steps the origin (next row of the
+  // strip, else next strip, else next image) with compares.
   auto tile_o = [&](int t) __attribute__((always_inline)) {
     const int b = t / tiles_img, rem = t - b * tiles_img;
     const int tx = rem / tiles_y;
@@ -154,13 +218,34 @@ __global__ __launch_bounds__(256, 1) void l1block_kernel(L1BlockArgs a) {
     o.base = ((b * a.H + o.oy0) * a.W + o.ox0) * 128;
     return o;
   };
-  // (branch-free: the bounds test is VALU in the MFMA shadow; only the piece
-  // count per wave is a uniform branch)
-  auto issue_piece = [&](int k, const TileO& o, int buf, bool cont) __attribute__((always_inline)) {
-    if (wave + NW * k >= NDP || (cont && wave + NW * k < QSKIP)) return;  // uniform
-    const int Y = DYX[k] & 0xFFFF, X = DYX[k] >> 16;
-    const bool ok = (unsigned)(o.oy0 - 2 + Y) < (unsigned)a.H && (unsigned)(o.ox0 - 2 + X) < (unsigned)a.W;
-    dma16_m0(rx, ok ? o.base + DREL[k] : BAD, lds0 + buf * PATCH + (wave + NW * k) * 1024);
+  const int row_b = a.W * 128, img_b = a.H * row_b;  // bytes of a pixel row, of an image
+  auto tile_step = [&](const TileO& o) __attribute__((always_inline)) {
+    TileO n;
+    n.oy0 = o.oy0 + 16;
+    n.ox0 = o.ox0;
+    n.base = o.base + 16 * row_b;
+    if (n.oy0 == a.H) {  // the next strip: up one image height, 16 pixels right
+      n.oy0 = 0;
+      n.ox0 += 16;
+      n.base += 16 * 128 - img_b;
+      if (n.ox0 == a.W) {  // the next image: back one row, on one image
+        n.ox0 = 0;
+        n.base += img_b - row_b;
+      }
+    }
+    return n;
+  };
+  // piece k with table entry e into the buffer whose first piece of this wave
+  // is at LDS address dst0.  Branch-free but where a wave may not have the
+  // piece (uniform): k = QP - 1 exists on waves 0, 1 only, and a continuation
+  // tile skips pieces q < QSKIP, each wave's first ones (k < 3)
+  auto issue_piece = [&](auto kc, int e, int pbase, int pmask, unsigned dst0, bool cont) __attribute__((always_inline)) {
+    constexpr int k = decltype(kc)::value;
+    if constexpr (NW * k + NW - 1 >= NDP)
+      if (wave + NW * k >= NDP) return;
+    if constexpr (NW * k < QSKIP)
+      if (cont && wave + NW * k < QSKIP) return;
+    l1b_dma16<k * NW * 1024>(rx, (e & pmask) ? BAD : pbase + (int)((unsigned)e << 4), dst0);
   };
 
   // ---- weights of both convs into registers: lane (fr, fg) of K-step s =
@@ -180,8 +265,14 @@ __global__ __launch_bounds__(256, 1) void l1block_kernel(L1BlockArgs a) {
     const float* src = tid < 16 ? a.b1 + 4 * tid : a.b2 + 4 * (tid - 16);
     *(float4*)(smem + OFF_B + 16 * tid) = *(const float4*)src;
   }
-#pragma unroll
-  for (int k = 0; k < QP; ++k) issue_piece(k, tile_o(tp_begin), 0, false);
+  TileO ocur = tile_o(tp_begin);
+  const unsigned dstw = __builtin_amdgcn_readfirstlane(lds0 + wave * 1024);  // this wave's piece 0 in buffer 0
+  l1b_for<QP>([&](auto kc) __attribute__((always_inline)) {
+    constexpr int k = decltype(kc)::value;
+    const int e = piece_entry(k);
+    tab[64 * k] = e;
+    issue_piece(kc, e, patch_base(ocur), patch_mask(ocur), dstw, false);
+  });
 
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
@@ -190,7 +281,8 @@ __global__ __launch_bounds__(256, 1) void l1block_kernel(L1BlockArgs a) {
 
   // diagnostic build (-DSAD_STAMPS=1): s_memtime of waves 0 and 2 of
   // workgroup 0 per tile -- 0 tile start, 1 conv1 issued, 2 after the
-  // intermediate barrier, 3 conv2 issued, 4 after the tile barrier
+  // intermediate barrier, 3 conv2 issued, 4 after the tile barrier; slot 5
+  // is stamped by a strip-start tile, slot 6 by a continuation tile
   const bool stamp_on = SAD_STAMPS && a.stamps && blockIdx.x == 0 && (wave == 0 || wave == 2);
   auto stamp = [&](int g, int slot) __attribute__((always_inline)) {
     if constexpr (SAD_STAMPS) {
@@ -203,47 +295,78 @@ __global__ __launch_bounds__(256, 1) void l1block_kernel(L1BlockArgs a) {
       }
     }
   };
+  // ---- lane constants of the tile loop, once per launch (LDS byte addresses,
+  // the LDS base included).  Those into the patch start in buffer 0 and are
+  // moved to the other buffer after every tile: PATCH is a multiple of 128, so
+  // it commutes with the XORs on the chunk bits 4-6 that the reads apply.
+  const int LY = 2 + 8 * pg + (fr >> 1), e01 = fr & 1;  // the leftover fragment: pixel (LY, 16 + e01)
+  // conv1 reads -- aligned fragment k, tap (ky, kx), K-half h: (LAp[kx] ^ sg) +
+  // (k + ky) PROW with sg = 2 (Y & 3) ^ 4 h as chunk bits, a constant; leftover
+  // fragment: L9[ky][kx] ^ 64 h
+  int LAp[3], L9[3][3];
+#pragma unroll
+  for (int kx = 0; kx < 3; ++kx) {
+    LAp[kx] = (int)lds0 + (2 + 8 * pg) * PROW + (fr + kx) * 128 + ((fg ^ l1b_key(fr + kx)) << 4);
+#pragma unroll
+    for (int ky = 0; ky < 3; ++ky)
+      L9[ky][kx] = (int)lds0 + ((LY + ky) * PWD + 16 + e01 + kx) * 128 +
+                   ((fg ^ l1b_key(16 + e01 + kx) ^ (((LY + ky) & 3) << 1)) << 4);
+  }
+  // conv1's intermediate stores: aligned fragment k at E1A[i] + k IROW, the
+  // leftover at E1L[i].  Channel tile 1 is chunk + 2: position (c + 2) ^ key =
+  // (c ^ key) ^ 2 (c even); the XOR stays inside the pixel (the padded row
+  // pitch is not a multiple of 64 B)
+  int E1A[2], E1L[2];
+  {
+    const int pa = (((cw >> 3) + (fg >> 1)) ^ l1b_key(fr)) * 16 + (fg & 1) * 8;
+    const int pl = (((cw >> 3) + (fg >> 1)) ^ l1b_key(16 + e01)) * 16 + (fg & 1) * 8;
+    const int xa = (int)lds0 + OFF_I + (2 + 8 * pg) * IROW + fr * 128;
+    const int xl = (int)lds0 + OFF_I + LY * IROW + (16 + e01) * 128;
+    E1A[0] = xa + pa, E1A[1] = xa + (pa ^ 32);
+    E1L[0] = xl + pl, E1L[1] = xl + (pl ^ 32);
+  }
+  // conv2: the residual of output row 8pg + jj, channels cw + 16 i + 4 fg, from
+  // the patch centre: (LRr[i] ^ 32 ((jj + 2) & 3)) + (jj + 2) PROW; the
+  // intermediate fragment of row 8pg + jj, tap (ky, kx), K-half h: I2[kx][h] +
+  // (jj + ky) IROW; the biases (b1 at BA + 64 i, b2 at BA + 256 + 64 i); the
+  // lane's part of an output store's offset
+  int LRr[2], I2[3][2];
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+    LRr[i] = (int)lds0 + pg * 8 * PROW + (fr + 2) * 128 +
+             ((((cw >> 3) + 2 * i + (fg >> 1)) ^ l1b_key(fr + 2)) << 4) + (fg & 1) * 8;
+#pragma unroll
+  for (int kx = 0; kx < 3; ++kx)
+#pragma unroll
+    for (int h = 0; h < 2; ++h)
+      I2[kx][h] = (int)lds0 + OFF_I + pg * 8 * IROW + (((fr + kx) * 128 + ((fg ^ l1b_key(fr + kx)) << 4)) ^ (h << 6));
+  const int BA = (int)lds0 + OFF_B + (cw + fg * 4) * 4;
+  const int OV = fr * 128 + (cw + 4 * fg) * 2;
+
   int pb = 0;
   for (int t = tp_begin; t < tp_end; ++t) {
     stamp(t - tp_begin, 0);
     const bool has_next = t + 1 < tp_end;
     // the next tile's patch (after the last tile: this tile's again, into the
     // free buffer, which nothing reads -- no branch around the DMA)
-    const TileO onext = tile_o(has_next ? t + 1 : t);
-    const int b = t / tiles_img, rem = t - b * tiles_img;
-    const int tx = rem / tiles_y, ty = rem - tx * tiles_y;
-    const int oy0 = ty * 16, ox0 = tx * 16;
+    const TileO ostep = tile_step(ocur);
+    const TileO onext = has_next ? ostep : ocur;
+    const int oy0 = ocur.oy0, ox0 = ocur.ox0;
     // continuation tile (uniform): the previous tile is the one above it, so
     // intermediate rows 0, 1 and patch rows 2, 3 are copies of its rows 16, 17
     // and 18, 19 (LDS to LDS), and conv1 computes rows 2-17 only: 18 fragments
     // instead of 21, 40 patch pieces instead of 50
-    const bool cont = t > tp_begin && ty > 0;
+    const bool cont = t > tp_begin && oy0 > 0;
     const bool next_cont = has_next && onext.oy0 > 0;
-    const int pbo = pb * PATCH;
-    const int pboa = pbo + (2 + 8 * pg) * PROW;  // aligned fragments: rows 2 + 8pg + k
-    // Lane constants, derived per tile from an opaque copy of the lane id:
-    // the fragment addresses are tile-invariant, and hoisted out of the tile
-    // loop they would take registers next to the 288 of resident weights.
+    stamp(t - tp_begin, cont ? 6 : 5);
+    const int pbo = pb * PATCH, pbn = PATCH - pbo;  // this tile's patch buffer, the next tile's
+    const int npbase = patch_base(onext), npmask = patch_mask(onext);
+    // what is still derived per tile comes from an opaque copy of the lane id,
+    // so that it takes no register across the tile
     int ln;
     asm volatile("v_mov_b32 %0, %1" : "=v"(ln) : "v"(lane));
     const int frt = ln & 15, fgt = ln >> 4, et = ln & 1;
-    // aligned fragment, patch column frt + kx: pixel row + chunk position of channel group fgt
-    int LAt[3], KXt[3];
-#pragma unroll
-    for (int kx = 0; kx < 3; ++kx) {
-      LAt[kx] = (frt + kx) * 128 + ((fgt ^ l1b_key(frt + kx)) << 4);
-      KXt[kx] = fgt ^ l1b_key(16 + et + kx);
-    }
-    // the leftover fragment: pixel (LYt, 16 + et), rows 2 + 8pg .. 9 + 8pg
-    const int LYt = 2 + 8 * pg + (frt >> 1);
-    // per-tile read bases: aligned (+ the patch buffer and the wave's row
-    // block), leftover (+ buffer) and the leftover row terms per tap row
-    int LAp[3], LYG[3];
-#pragma unroll
-    for (int kx = 0; kx < 3; ++kx) LAp[kx] = LAt[kx] + pboa;
-    const int LRb = (LYt * PWD + 16 + et) * 128 + pbo;
-#pragma unroll
-    for (int ky = 0; ky < 3; ++ky) LYG[ky] = ((LYt + ky) & 3) << 1;
+    int pe = tab[0];  // the table entry of the next piece, read one piece ahead
 
     // ---------------- conv1: 18 x 18 intermediate ----------------
     // Unit = one fragment read + its two MFMAs (channel tiles i = 0, 1).
@@ -254,23 +377,21 @@ __global__ __launch_bounds__(256, 1) void l1block_kernel(L1BlockArgs a) {
     // among fragment k's MFMAs instead of after all of them (one wave per
     // SIMD: VALU work only hides in the MFMA shadow).  The bias is the first
     // MFMA's C operand.
-    auto rd1 = [&](auto uc) __attribute__((always_inline)) -> uint4 {
+    auto rd1 = [&](auto uc) __attribute__((always_inline)) -> l1b_v4 {
       constexpr int u = decltype(uc)::value;
       constexpr int s = l1b_s1(u), k = l1b_k1(u);
       constexpr int tap = s >> 1, h = s & 1, ky = tap / 3, kx = tap % 3;
       if constexpr (k < NA) {
         // patch row Y = 2 + 8pg + k + ky: Y & 3 is a constant
         constexpr int sg = (((2 + k + ky) & 3) << 5) ^ (h << 6);  // 2 (Y & 3) and the K-half, as chunk bits
-        // (pboa is a multiple of 128, so it commutes with the XOR on bits 4-6)
-        return *(const uint4*)(smem + (LAp[kx] ^ sg) + (k + ky) * PROW);
+        return l1b_ld<l1b_v4>((LAp[kx] ^ sg) + (k + ky) * PROW);
       } else {
-        const int pos = KXt[kx] ^ LYG[ky] ^ (h << 2);
-        return *(const uint4*)(smem + (LRb + (pos << 4)) + (ky * PWD + kx) * 128);
+        return l1b_ld<l1b_v4>(h ? L9[ky][kx] ^ 64 : L9[ky][kx]);
       }
     };
     f32x4 b1v[2];
 #pragma unroll
-    for (int i = 0; i < 2; ++i) b1v[i] = *(const f32x4*)(smem + OFF_B + (cw + 16 * i + fgt * 4) * 4);
+    for (int i = 0; i < 2; ++i) b1v[i] = l1b_ld<f32x4>(BA + 64 * i);
     // column masks of this tile's intermediate pixels (0: outside the image):
     // aligned fragments x = frt, leftovers x = 16 + et
     const uint32_t cma = (unsigned)(ox0 - 1 + frt) < (unsigned)a.W ? 0xFFFFFFFFu : 0u;
@@ -279,35 +400,23 @@ __global__ __launch_bounds__(256, 1) void l1block_kernel(L1BlockArgs a) {
     // epilogue of fragment k in 4 parts (channel tile i = part / 2; first or
     // second half of the 4 values), so it can be spread between MFMAs
     uint32_t e1_inm = 0, e1_qx = 0;
-    int e1_addr = 0, e1_addr1 = 0;
     auto epi1 = [&](auto kc, auto pc) __attribute__((always_inline)) {
       constexpr int k = decltype(kc)::value, part = decltype(pc)::value, i = part >> 1;
       if constexpr (part == 0) {
-        int y, x;
-        if constexpr (k < NA) {
-          y = 2 + 8 * pg + k;
-          x = frt;
-          e1_inm = (unsigned)(oy0 - 1 + y) < (unsigned)a.H ? cma : 0u;  // row test uniform
-        } else {
-          y = LYt;
-          x = 16 + et;
-          e1_inm = (unsigned)(oy0 - 1 + y) < (unsigned)a.H ? cml : 0u;
-        }
-        // channel tile 1 is chunk + 2: position (c + 2) ^ key = (c ^ key) ^ 2 (c
-        // even); the XOR stays inside the pixel (the padded row pitch is not a
-        // multiple of 64 B)
-        const int pix = OFF_I + y * IROW + x * 128;
-        const int pos = (((cw >> 3) + (fgt >> 1)) ^ l1b_key(x)) * 16 + (fgt & 1) * 8;
-        e1_addr = pix + pos;
-        e1_addr1 = pix + (pos ^ 32);
+        if constexpr (k < NA)
+          e1_inm = (unsigned)(oy0 - 1 + 2 + 8 * pg + k) < (unsigned)a.H ? cma : 0u;  // row test uniform
+        else
+          e1_inm = (unsigned)(oy0 - 1 + 2 + 8 * pg + (frt >> 1)) < (unsigned)a.H ? cml : 0u;
       }
       if constexpr ((part & 1) == 0) {
-        e1_qx = l1b_relu2(l1b_pk(acc[i][k][0], acc[i][k][1])) & e1_inm;
+        // (the mask, all ones or zero, commutes with the ReLU; applied first,
+        // no VALU reads v_pk_max_i16's result right behind it: that costs an s_nop)
+        e1_qx = l1b_relu2(l1b_pk(acc[i][k][0], acc[i][k][1]) & e1_inm);
       } else {
-        uint2 q;
+        l1b_v2 q;
         q.x = e1_qx;
-        q.y = l1b_relu2(l1b_pk(acc[i][k][2], acc[i][k][3])) & e1_inm;
-        if (!(ab & 2)) *(uint2*)(smem + (i ? e1_addr1 : e1_addr)) = q;
+        q.y = l1b_relu2(l1b_pk(acc[i][k][2], acc[i][k][3]) & e1_inm);
+        if (!(ab & 2)) l1b_st<l1b_v2>(k < NA ? E1A[i] + k * IROW : E1L[i], q);
       }
     };
     if (cont) {
@@ -339,19 +448,20 @@ __global__ __launch_bounds__(256, 1) void l1block_kernel(L1BlockArgs a) {
         auto rdp = [&](int st) __attribute__((always_inline)) {
           const int tap = st >> 1, h = st & 1, ky = tap / 3, kx = tap % 3;
           const int Y = y + ky;
-          const int ad = left ? pbo + (Y * PWD + 16 + et + kx) * 128 +
-                                    ((KXt[kx] ^ ((Y & 3) << 1) ^ (h << 2)) << 4)
-                              : pbo + (LAt[kx] ^ (((Y & 3) << 5) ^ (h << 6))) + Y * PROW;
-          return *(const uint4*)(smem + ad);
+          // (aligned: LAp is the address for patch row 2 + 8pg)
+          const int ad = left ? (int)lds0 + pbo + (Y * PWD + 16 + et + kx) * 128 +
+                                    ((fgt ^ l1b_key(16 + et + kx) ^ ((Y & 3) << 1) ^ (h << 2)) << 4)
+                              : (LAp[kx] ^ (((Y & 3) << 5) ^ (h << 6))) + (Y - 2 - 8 * pg) * PROW;
+          return l1b_ld<l1b_v4>(ad);
         };
         // 4 fragment reads in flight (a read per 2 dependent MFMAs would
         // otherwise wait out the LDS latency every K-step)
-        uint4 pq[4];
+        l1b_v4 pq[4];
 #pragma unroll
         for (int st = 0; st < 4; ++st) pq[st] = rdp(st);
 #pragma unroll
         for (int st = 0; st < NS; ++st) {
-          const uint4 bf = pq[st & 3];
+          const l1b_v4 bf = pq[st & 3];
           if (st + 4 < NS) pq[st & 3] = rdp(st + 4);
 #pragma unroll
           for (int i = 0; i < 2; ++i) {
@@ -379,15 +489,17 @@ __global__ __launch_bounds__(256, 1) void l1block_kernel(L1BlockArgs a) {
       prefix(false);
       if (pg == 0) prefix(true);
     }
-    uint4 bq[DQ];
+    l1b_v4 bq[DQ];
     l1b_for<DQ>([&](auto uc) __attribute__((always_inline)) { bq[decltype(uc)::value] = rd1(uc); });
     l1b_for<NU1>([&](auto uc) __attribute__((always_inline)) {
       constexpr int u = decltype(uc)::value;
       constexpr int s = l1b_s1(u), k = l1b_k1(u);
-      const uint4 bf = bq[u % DQ];
+      const l1b_v4 bf = bq[u % DQ];
       if constexpr (u + DQ < NU1) bq[u % DQ] = rd1(std::integral_constant<int, u + DQ>{});
-      if constexpr (u % 5 == 0 && u / 5 < QP)
-        if (!(ab & 1)) issue_piece(u / 5, onext, pb ^ 1, next_cont);
+      if constexpr (u % 5 == 0 && u / 5 < QP) {
+        if (!(ab & 1)) issue_piece(std::integral_constant<int, u / 5>{}, pe, npbase, npmask, dstw + pbn, next_cont);
+        if constexpr (u / 5 + 1 < QP) pe = tab[64 * (u / 5 + 1)];
+      }
 #pragma unroll
       for (int i = 0; i < 2; ++i) {
         if constexpr (s == 0)
@@ -419,24 +531,17 @@ __global__ __launch_bounds__(256, 1) void l1block_kernel(L1BlockArgs a) {
     l1b_for<4>([&](auto pc) __attribute__((always_inline)) { epi1(std::integral_constant<int, NF - 1>{}, pc); });
 
     // conv2's accumulators start at b2 + x (the identity): residual of output
-    // row 8pg + jj, channels cw + 16 i + 4 fg2, from the patch centre
-    int ln2;
-    asm volatile("v_mov_b32 %0, %1" : "=v"(ln2) : "v"(lane));
-    const int fr2 = ln2 & 15, fg2 = ln2 >> 4;
-    int LRr[2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-      LRr[i] = (fr2 + 2) * 128 + ((((cw >> 3) + 2 * i + (fg2 >> 1)) ^ l1b_key(fr2 + 2)) << 4) + (fg2 & 1) * 8;
+    // row 8pg + jj, channels cw + 16 i + 4 fg, from the patch centre
     f32x4 acc2[2][8];
     // in two halves: the bias and residual reads are issued a few units before
     // the adds that consume them, so the wait for them is not a wait for the
     // youngest LDS read (lgkmcnt(0) would drain the fragment reads in flight)
     f32x4 i2b[2];
-    uint2 i2r[2];
+    l1b_v2 i2r[2];
     auto init2_rd = [&](auto jc, auto ic) __attribute__((always_inline)) {
       constexpr int jj = decltype(jc)::value, i = decltype(ic)::value;
-      i2b[i] = *(const f32x4*)(smem + OFF_B + 256 + (cw + 16 * i + fg2 * 4) * 4);
-      i2r[i] = *(const uint2*)(smem + ((LRr[i] ^ (((jj + 2) & 3) << 5)) + pbo + pg * 8 * PROW) + (jj + 2) * PROW);
+      i2b[i] = l1b_ld<f32x4>(BA + 256 + 64 * i);
+      i2r[i] = l1b_ld<l1b_v2>((LRr[i] ^ (((jj + 2) & 3) << 5)) + (jj + 2) * PROW);
     };
     auto init2_add = [&](auto jc, auto ic) __attribute__((always_inline)) {
       constexpr int jj = decltype(jc)::value, i = decltype(ic)::value;
@@ -460,19 +565,13 @@ __global__ __launch_bounds__(256, 1) void l1block_kernel(L1BlockArgs a) {
     // Fragment-outer throughout: fragment jj-1's epilogue (ReLU, bf16, 8-B
     // stores) and fragment jj+1's accumulator init go among fragment jj's MFMAs.
     // conv2: intermediate fragments of output rows 8pg + jj
-    int I2[3][2];
-#pragma unroll
-    for (int kx = 0; kx < 3; ++kx)
-#pragma unroll
-      for (int h = 0; h < 2; ++h)
-        I2[kx][h] = OFF_I + pg * 8 * IROW + (((fr2 + kx) * 128 + ((fg2 ^ l1b_key(fr2 + kx)) << 4)) ^ (h << 6));
-    auto rd2 = [&](auto uc) __attribute__((always_inline)) -> uint4 {
+    auto rd2 = [&](auto uc) __attribute__((always_inline)) -> l1b_v4 {
       constexpr int u = decltype(uc)::value;
       constexpr int s = u % NS, jj = u / NS;
       constexpr int tap = s >> 1, h = s & 1, ky = tap / 3, kx = tap % 3;
-      return *(const uint4*)(smem + I2[kx][h] + (jj + ky) * IROW);
+      return l1b_ld<l1b_v4>(I2[kx][h] + (jj + ky) * IROW);
     };
-    const int obase = ((b * a.H + oy0 + 8 * pg) * a.W + ox0) * 128;  // uniform
+    const int obase = ocur.base + 8 * pg * row_b;  // uniform
     // epilogue of fragment jj in 4 parts, as conv1's
     uint32_t e2_qx = 0;
     auto epi2 = [&](auto jc, auto pc) __attribute__((always_inline)) {
@@ -485,7 +584,7 @@ __global__ __launch_bounds__(256, 1) void l1block_kernel(L1BlockArgs a) {
         q.y = l1b_relu2(l1b_pk(acc2[i][jj][2], acc2[i][jj][3]));
         if (!(ab & 4))
           __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(l1b_v2, q), ro,
-                                                (jj * a.W + fr2) * 128 + (cw + 16 * i + 4 * fg2) * 2, obase, 0);
+                                                OV + 32 * i, obase + jj * row_b, 0);
       }
     };
     // the next tile continues this strip: its patch rows 2, 3 are this patch's
@@ -501,12 +600,12 @@ __global__ __launch_bounds__(256, 1) void l1block_kernel(L1BlockArgs a) {
     l1b_for<NU2>([&](auto uc) __attribute__((always_inline)) {
       constexpr int u = decltype(uc)::value;
       constexpr int s = u % NS, jj = u / NS;
-      const uint4 bf = bq[u % DQ];
+      const l1b_v4 bf = bq[u % DQ];
       if constexpr (u + DQ < NU2) bq[u % DQ] = rd2(std::integral_constant<int, u + DQ>{});
       if constexpr (u == 3) {
         if (next_cont) {
-          *(uint4*)(smem + (pb ^ 1) * PATCH + 40 * 128 + tid * 16) = pcv0;
-          *(uint4*)(smem + (pb ^ 1) * PATCH + 40 * 128 + pci1 * 16) = pcv1;
+          *(uint4*)(smem + pbn + 40 * 128 + tid * 16) = pcv0;
+          *(uint4*)(smem + pbn + 40 * 128 + pci1 * 16) = pcv1;
         }
       }
       l1b_for<2>([&](auto ic) __attribute__((always_inline)) {
@@ -550,10 +649,23 @@ __global__ __launch_bounds__(256, 1) void l1block_kernel(L1BlockArgs a) {
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
     stamp(t - tp_begin, 4);
+    // the patch addresses move to the other buffer
+    const int dpb = pbn - pbo;
+#pragma unroll
+    for (int kx = 0; kx < 3; ++kx) {
+      LAp[kx] += dpb;
+#pragma unroll
+      for (int ky = 0; ky < 3; ++ky) L9[ky][kx] += dpb;
+    }
+    LRr[0] += dpb, LRr[1] += dpb;
     pb ^= 1;
+    ocur = ostep;
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
+
+__global__ __launch_bounds__(256, 1) void l1block_kernel(L1BlockArgs a) { l1block_body<false>(a); }
+__global__ __launch_bounds__(256, 1) void l1block_ablate_kernel(L1BlockArgs a) { l1block_body<true>(a); }
 
 int launch_l1block(const L1BlockArgs& a_in, hipStream_t s) {
   using namespace l1b;
@@ -566,6 +678,8 @@ int launch_l1block(const L1BlockArgs& a_in, hipStream_t s) {
   static bool attr = false;
   if (!attr) {
     SAD_CHECK_HIP(hipFuncSetAttribute((const void*)l1block_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM));
+    SAD_CHECK_HIP(
+        hipFuncSetAttribute((const void*)l1block_ablate_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM));
     attr = true;
   }
   // the patch DMA addresses the input through 32-bit buffer offsets: split a
@@ -586,29 +700,35 @@ int launch_l1block(const L1BlockArgs& a_in, hipStream_t s) {
     SAD_CHECK_HIP(hipMemsetAsync(sbuf, 0, 2 * 8192 * 8, s));
     a.stamps = sbuf;
 #endif
-    hipLaunchKernelGGL(l1block_kernel, dim3((unsigned)g), dim3(256), SMEM, s, a);
+    if (a.ablate == 0)
+      hipLaunchKernelGGL(l1block_kernel, dim3((unsigned)g), dim3(256), SMEM, s, a);
+    else
+      hipLaunchKernelGGL(l1block_ablate_kernel, dim3((unsigned)g), dim3(256), SMEM, s, a);
     SAD_CHECK_HIP(hipGetLastError());
 #if SAD_STAMPS
     {  // per-tile phase averages of waves 0 and 2 of workgroup 0 (skipping the first tile)
       std::vector<uint64_t> h(2 * 8192);
       SAD_CHECK_HIP(hipStreamSynchronize(s));
       SAD_CHECK_HIP(hipMemcpy(h.data(), sbuf, h.size() * 8, hipMemcpyDeviceToHost));
-      for (int wv = 0; wv < 2; ++wv) {
-        double ph[5] = {0, 0, 0, 0, 0};
-        int n = 0;
-        for (int t = 1; t + 1 < 1024; ++t) {
-          const uint64_t* c = &h[(size_t)wv * 8192 + (size_t)t * 8];
-          const uint64_t nxt = h[(size_t)wv * 8192 + (size_t)(t + 1) * 8];
-          if (!c[0] || !c[4] || !nxt) break;
-          for (int k = 0; k < 4; ++k) ph[k] += (double)(c[k + 1] - c[k]);
-          ph[4] += (double)(nxt - c[4]);
-          ++n;
+      for (int wv = 0; wv < 2; ++wv)
+        for (int kind = 0; kind < 2; ++kind) {  // 0 strip-start tiles, 1 continuation tiles
+          double ph[5] = {0, 0, 0, 0, 0};
+          int n = 0;
+          for (int t = 1; t + 1 < 1024; ++t) {
+            const uint64_t* c = &h[(size_t)wv * 8192 + (size_t)t * 8];
+            const uint64_t nxt = h[(size_t)wv * 8192 + (size_t)(t + 1) * 8];
+            if (!c[0] || !c[4] || !nxt) break;
+            if (!c[5 + kind]) continue;
+            for (int k = 0; k < 4; ++k) ph[k] += (double)(c[k + 1] - c[k]);
+            ph[4] += (double)(nxt - c[4]);
+            ++n;
+          }
+          if (n)
+            fprintf(stderr, "l1block stamps N=%d wave %d %s: %d tiles, cycles conv1 %.1f | epi1+B1 %.1f | conv2 %.1f | "
+                    "epi2+B2 %.1f | loop %.1f | total %.1f\n", a.N, 2 * wv, kind ? "continuation" : "strip-start", n,
+                    ph[0] / n, ph[1] / n, ph[2] / n, ph[3] / n, ph[4] / n,
+                    (ph[0] + ph[1] + ph[2] + ph[3] + ph[4]) / n);
         }
-        if (n)
-          fprintf(stderr, "l1block stamps N=%d wave %d: %d tiles, cycles conv1 %.0f | epi1+B1 %.0f | conv2 %.0f | "
-                  "epi2+B2 %.0f | loop %.0f | total %.0f\n", a.N, 2 * wv, n, ph[0] / n, ph[1] / n, ph[2] / n,
-                  ph[3] / n, ph[4] / n, (ph[0] + ph[1] + ph[2] + ph[3] + ph[4]) / n);
-      }
     }
 #endif
   }

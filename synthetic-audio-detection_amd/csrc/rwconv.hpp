@@ -33,6 +33,16 @@ __device__ __forceinline__ void l1b_mfma_v0(f32x4& acc, const l1b_v4& w, const u
 __device__ __forceinline__ void l1b_mfma_v(f32x4& acc, const l1b_v4& w, const uint4& b) {
   asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+v"(acc) : "v"(w), "v"(__builtin_bit_cast(l1b_v4, b)));
 }
+// the same with the fragment as a native vector (HIP's uint4 is a struct)
+__device__ __forceinline__ void l1b_mfma_a(f32x4& acc, const l1b_v4& w, const l1b_v4& b) {
+  asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+v"(acc) : "a"(w), "v"(b));
+}
+__device__ __forceinline__ void l1b_mfma_ac(f32x4& acc, const l1b_v4& w, const l1b_v4& b, const f32x4& c) {
+  asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %3" : "=&v"(acc) : "a"(w), "v"(b), "v"(c));
+}
+__device__ __forceinline__ void l1b_mfma_v(f32x4& acc, const l1b_v4& w, const l1b_v4& b) {
+  asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+v"(acc) : "v"(w), "v"(b));
+}
 // two floats -> packed bf16 pair (RNE), one v_cvt_pk_bf16_f32
 typedef __bf16 l1b_bf2 __attribute__((ext_vector_type(2)));
 typedef float l1b_f2 __attribute__((ext_vector_type(2)));
