@@ -184,6 +184,52 @@ int sad_resample_run(const sad_resample_plan* plan, const float* x, int64_t n_in
 int sad_window_absmax_run(const float* wav, int64_t n, int64_t window, int64_t hop, int64_t n_windows,
                           float* out, void* stream);
 
+/* ------------------------------------------------------ trainer ingestion */
+/* SpectrogramDataset.__getitem__'s load, resample and 2-segment rule
+ * (submodel_trainer.py:143-187) for a whole batch of files in ONE launch.  The
+ * files' samples sit as stored (interleaved int16, or host-decoded fp32) in one
+ * byte arena on the device; only the head of a file that the two segments read
+ * has to be there.
+ *
+ * sad_train_ingest_need_frames: the frames of a file at orig_freq that the
+ * first 2 seg_len samples at new_freq read:
+ *   2 seg_len                                      orig_freq == new_freq
+ *   ((2 seg_len - 1) / new) orig + orig + width    otherwise (orig, new reduced by
+ *                                                  their gcd; width as in the plan)
+ * A host reads min(total frames, need) frames of each file.
+ *
+ * file_table [n_files][6] int64, one row per file:
+ *   0 byte offset of the file's first sample in the arena (a multiple of 16)
+ *   1 frames present in the arena (<= total frames)
+ *   2 total frames of the file (sets its resampled length n_out =
+ *     sad_resample_out_len, or the frame count at the target rate)
+ *   3 channels (1..64)          4 sad_pcm_format          5 index into rate_plans
+ * rate_plans [n_rates <= 8]: the resample plan of each source rate to the
+ * target rate, NULL for the target rate itself.
+ *
+ * out [2 n_files][seg_len] fp32.  Row 2f + s, sample i, with m = s seg_len + i:
+ * 0 for m >= n_out, else the mono mix of sad_pcm_mono_run fed to the polyphase
+ * sum of sad_resample_run (same operations in the same order: the bits that
+ * the two calls give on the whole file); samples past the frames present count
+ * as 0.  A file with n_out < 2 seg_len gives its first segment (zero-padded when
+ * n_out < seg_len) in both rows.  The caller drops files shorter than the
+ * reference's 0.9 seg_len rule beforehand.
+ *
+ * Workgroups are (file, tile) pairs: tiles [n_tiles][2] int32 lists, per file
+ * in any order, tile = 0 .. sad_train_ingest_file_tiles(...) - 1.  file_table
+ * is read on the HOST for the argument checks; d_file_table (the same values)
+ * and d_tiles are DEVICE copies, normally uploaded with the arena in one copy.
+ * A rate with fewer than 64 phases whose 1024-output input span exceeds 8192
+ * samples (beyond 192 kHz -> 32 kHz) is refused.  Asynchronous on `stream`:
+ * one launch, no allocation, no atomics, no host synchronisation. */
+int sad_train_ingest_need_frames(int32_t orig_freq, int32_t new_freq, int64_t seg_len, int64_t* need);
+int sad_train_ingest_file_tiles(int32_t orig_freq, int32_t new_freq, int64_t total_frames, int64_t seg_len,
+                                int64_t* n_tiles);
+int sad_train_ingest_run(const void* arena, int64_t arena_bytes, const int64_t* file_table,
+                         const int64_t* d_file_table, int64_t n_files, const int32_t* d_tiles, int64_t n_tiles,
+                         const sad_resample_plan* const* rate_plans, int32_t n_rates, int64_t seg_len, float* out,
+                         void* stream);
+
 /* --------------------------------------------------------- catalogue scan */
 /* Many files in one run (sad/scan.py, catalog_runner.py): the files' mono
  * 32 kHz waveforms sit back to back in ONE fp32 arena; the device picks the

@@ -157,15 +157,163 @@ static unsigned grid_for(int64_t n) {
   return (unsigned)(g < 65536 ? (g > 0 ? g : 1) : 65536);
 }
 
-}  // namespace sad
+// ---- trainer ingestion: one launch per batch of stored files ------------------
+// SpectrogramDataset.__getitem__'s load + resample + 2-segment rule
+// (submodel_trainer.py:143-187 of the reference) for a whole batch: the files'
+// samples sit as stored (interleaved int16 / fp32) in one byte arena, and file f
+// gives rows 2f and 2f + 1 of out [2 n_files, seg_len].  With n_out the file's
+// 32 kHz length, row 2f + s holds samples m = s * seg_len + i of the resampled
+// mono signal (0 for m >= n_out); a file with n_out < 2 seg_len repeats its
+// first segment, which is computed once and stored twice.  Every sample is
+// pcm_mono_kernel's value fed to resample_kernel's sum (ascending k, one fmaf
+// per tap; a tap outside the samples read multiplies a zero, which leaves the
+// fp32 sum unchanged), so the rows are the bits the two-kernel path gives.
+//
+// A workgroup is one (file, tile) pair read from a table the host builds with
+// the batch.  Three block-uniform forms share the kernel:
+//   native    the file is at the target rate: mono mix straight to the rows;
+//   per-output (nw < 64: 16 / 48 / 96 kHz) TI_TILE consecutive outputs; the mono
+//             inputs they need are mixed into LDS once, each thread sums K taps;
+//   wide      (nw >= 64: 44.1 / 22.05 kHz) resample_wide_kernel's blocking, 64
+//             frames x 64 phases per tile, the mono mix done while staging.
+constexpr int TI_TILE = 1024;     // outputs per tile, native and per-output forms
+constexpr int TI_SPAN = 8192;     // LDS floats: the per-output form's input span
+constexpr int TI_MAX_RATES = 8;   // distinct sample rates in one launch
+constexpr int TI_COLS = 6;        // file table columns
+static_assert(TI_SPAN >= RS_WAVES * RS_KC * RS_R, "the wide form's staging fits the span buffer");
 
-using namespace sad;
+struct TrainRates {
+  const float* kt[TI_MAX_RATES];  // nullptr: the target rate itself
+  int orig[TI_MAX_RATES], nw[TI_MAX_RATES], width[TI_MAX_RATES], K[TI_MAX_RATES];
+};
 
-struct sad_resample_plan {
-  int32_t orig_freq = 0, new_freq = 0;
-  int orig = 1, nw = 1, width = 0, K = 0;  // reduced by the gcd
-  float* d_kt = nullptr;                    // [K][nw] fp32
-  int device = 0;
+// pcm_mono_kernel's value at frame i; 0 outside the frames that were read
+template <typename IT>
+__device__ __forceinline__ float ti_mono(const IT* __restrict__ x, int64_t i, int64_t n_read, int channels,
+                                         float fc) {
+  const float scale = sizeof(IT) == 2 ? (1.0f / 32768.0f) : 1.0f;
+  if (i < 0 || i >= n_read) return 0.f;
+  const IT* p = x + i * channels;
+  float s = (float)p[0] * scale;
+  for (int c = 1; c < channels; ++c) s += (float)p[c] * scale;
+  return channels == 1 ? s : s / fc;
+}
+
+template <typename IT>
+__device__ __forceinline__ void ti_tile(float* __restrict__ xs, const IT* __restrict__ x, int64_t n_read,
+                                        int64_t n_out, int channels, const float* __restrict__ kt, int orig, int nw,
+                                        int width, int K, int tile, int64_t seg_len, float* __restrict__ out0) {
+  const float fc = (float)channels;
+  const bool dup = n_out < 2 * seg_len;
+  const int64_t M = dup ? seg_len : 2 * seg_len;  // samples to produce; row 2f + 1 follows row 2f in memory
+  auto store = [&](int64_t m, float v) {
+    if (m < M) {
+      v = m < n_out ? v : 0.f;
+      out0[m] = v;
+      if (dup) out0[seg_len + m] = v;
+    }
+  };
+  if (!kt) {  // native rate
+    const int64_t m0 = (int64_t)tile * TI_TILE;
+#pragma unroll
+    for (int q = 0; q < TI_TILE / 256; ++q) {
+      const int64_t m = m0 + q * 256 + threadIdx.x;
+      if (m < M) store(m, ti_mono(x, m, n_read, channels, fc));
+    }
+    return;
+  }
+  if (nw < 64) {  // per-output form
+    const int64_t m0 = (int64_t)tile * TI_TILE;
+    const int64_t j0 = m0 / nw;
+    const int64_t span0 = j0 * orig - width;  // x index of xs[0]
+    const int64_t mlast = (m0 + TI_TILE < M ? m0 + TI_TILE : M) - 1;
+    const int cnt = mlast < m0 ? 0 : (int)((mlast / nw - j0) * orig) + K;  // <= TI_SPAN (checked on the host)
+    for (int e = threadIdx.x; e < cnt; e += 256) xs[e] = ti_mono(x, span0 + e, n_read, channels, fc);
+    __syncthreads();
+#pragma unroll 1
+    for (int q = 0; q < TI_TILE / 256; ++q) {
+      const int64_t m = m0 + q * 256 + threadIdx.x;
+      if (m >= M) continue;
+      const int64_t j = m / nw;
+      const int p = (int)(m - j * nw);
+      const float* xr = xs + (int)((j - j0) * orig);
+      const float* kp = kt + p;
+      float acc = 0.f;
+      for (int k = 0; k < K; ++k) acc = fmaf(xr[k], kp[k * nw], acc);
+      store(m, acc);
+    }
+    return;
+  }
+  // wide form: tile = frame tile * phase blocks + phase block
+  const int npb = (nw + 63) / 64;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int p = (tile % npb) * 64 + lane;
+  const bool pok = p < nw;
+  const int64_t j0 = ((int64_t)(tile / npb) * RS_WAVES + wave) * RS_R;  // this wave's first frame
+  float* xw = xs + wave * (RS_KC * RS_R);                               // xw[k][r]
+  float acc[RS_R];
+#pragma unroll
+  for (int r = 0; r < RS_R; ++r) acc[r] = 0.f;
+  for (int kc = 0; kc < K; kc += RS_KC) {
+    __syncthreads();  // the previous chunk's reads are done
+#pragma unroll 4
+    for (int e = lane; e < RS_KC * RS_R; e += 64) {
+      const int r = e % RS_R, k = e / RS_R;
+      const int64_t i = (j0 + r) * orig + kc + k - width;
+      xw[e] = kc + k < K ? ti_mono(x, i, n_read, channels, fc) : 0.f;
+    }
+    __syncthreads();
+    const int kn = K - kc < RS_KC ? K - kc : RS_KC;
+    const float* kp = kt + (int64_t)kc * nw + p;
+#pragma unroll 4
+    for (int k = 0; k < kn; ++k) {
+      const float w = pok ? kp[(int64_t)k * nw] : 0.f;
+      const float4* xr = (const float4*)(xw + k * RS_R);
+#pragma unroll
+      for (int q = 0; q < RS_R / 4; ++q) {
+        const float4 v = xr[q];
+        acc[4 * q + 0] = fmaf(v.x, w, acc[4 * q + 0]);
+        acc[4 * q + 1] = fmaf(v.y, w, acc[4 * q + 1]);
+        acc[4 * q + 2] = fmaf(v.z, w, acc[4 * q + 2]);
+        acc[4 * q + 3] = fmaf(v.w, w, acc[4 * q + 3]);
+      }
+    }
+  }
+  if (pok) {
+#pragma unroll
+    for (int r = 0; r < RS_R; ++r) store((j0 + r) * nw + p, acc[r]);
+  }
+}
+
+// file_table [n_files][TI_COLS] int64: byte offset, frames read, total frames,
+// channels, encoding, rate index; tiles [n_tiles][2] int32: file, tile
+__global__ __launch_bounds__(256) void train_ingest_kernel(const unsigned char* __restrict__ arena,
+                                                           const int64_t* __restrict__ file_table, int n_files,
+                                                           const int32_t* __restrict__ tiles, TrainRates rates,
+                                                           int64_t seg_len, float* __restrict__ out) {
+  __shared__ __attribute__((aligned(16))) float xs[TI_SPAN];
+  const int f = tiles[2 * (int64_t)blockIdx.x], tile = tiles[2 * (int64_t)blockIdx.x + 1];
+  if (f < 0 || f >= n_files || tile < 0) return;  // block-uniform
+  const int64_t* ft = file_table + (int64_t)f * TI_COLS;
+  const int64_t n_read = ft[1], total = ft[2];
+  const int channels = (int)ft[3], enc = (int)ft[4], ri = (int)ft[5];
+  const float* kt = rates.kt[ri];
+  const int orig = rates.orig[ri], nw = rates.nw[ri], width = rates.width[ri], K = rates.K[ri];
+  const int64_t n_out = kt ? (nw * total + orig - 1) / orig : total;
+  float* out0 = out + 2 * (int64_t)f * seg_len;
+  const unsigned char* x = arena + ft[0];
+  if (enc == SAD_PCM_I16)
+    ti_tile<int16_t>(xs, (const int16_t*)x, n_read, n_out, channels, kt, orig, nw, width, K, tile, seg_len, out0);
+  else
+    ti_tile<float>(xs, (const float*)x, n_read, n_out, channels, kt, orig, nw, width, K, tile, seg_len, out0);
+}
+
+// torchaudio's polyphase geometry for orig_freq -> new_freq (sinc_interp_hann,
+// lowpass_filter_width 6, rolloff 0.99): rates reduced by their gcd, the filter
+// half-width in input samples and the taps per output
+struct RsGeometry {
+  int orig, nw, width, K;
+  double base;
 };
 
 static int64_t gcd64(int64_t a, int64_t b) {
@@ -176,6 +324,42 @@ static int64_t gcd64(int64_t a, int64_t b) {
   }
   return a;
 }
+
+static RsGeometry rs_geometry(int32_t orig_freq, int32_t new_freq) {
+  const int64_t g = gcd64(orig_freq, new_freq);
+  RsGeometry q;
+  q.orig = (int)(orig_freq / g);
+  q.nw = (int)(new_freq / g);
+  q.base = (double)(q.orig < q.nw ? q.orig : q.nw) * 0.99;
+  q.width = (int)ceil(6 * (double)q.orig / q.base);
+  q.K = 2 * q.width + q.orig;
+  return q;
+}
+
+// tiles of one file (0 when the form cannot take the rate: the per-output
+// form's input span must fit TI_SPAN)
+static int64_t ti_file_tiles(bool native, const RsGeometry& q, int64_t total_frames, int64_t seg_len) {
+  const int64_t n_out = native ? total_frames : (q.nw * total_frames + q.orig - 1) / q.orig;
+  const int64_t M = n_out < 2 * seg_len ? seg_len : 2 * seg_len;
+  if (native) return (M + TI_TILE - 1) / TI_TILE;
+  if (q.nw < 64) {
+    if (((int64_t)(TI_TILE - 1) / q.nw + 1) * q.orig + q.K > TI_SPAN) return 0;
+    return (M + TI_TILE - 1) / TI_TILE;
+  }
+  const int64_t frames = (M + q.nw - 1) / q.nw;
+  return (frames + RS_WAVES * RS_R - 1) / (RS_WAVES * RS_R) * ((q.nw + 63) / 64);
+}
+
+}  // namespace sad
+
+using namespace sad;
+
+struct sad_resample_plan {
+  int32_t orig_freq = 0, new_freq = 0;
+  int orig = 1, nw = 1, width = 0, K = 0;  // reduced by the gcd
+  float* d_kt = nullptr;                    // [K][nw] fp32
+  int device = 0;
+};
 
 extern "C" int sad_pcm_mono_run(const void* pcm, int32_t format, int64_t frames, int32_t channels, float* out,
                                 int64_t out_len, void* stream) {
@@ -199,14 +383,11 @@ extern "C" int sad_pcm_mono_run(const void* pcm, int32_t format, int64_t frames,
 extern "C" int sad_resample_plan_create(int32_t orig_freq, int32_t new_freq, sad_resample_plan** out) {
   SAD_REQUIRE(out, "null out");
   SAD_REQUIRE(orig_freq > 0 && new_freq > 0, "sample rates must be positive");
-  const int64_t g = gcd64(orig_freq, new_freq);
-  const int orig = (int)(orig_freq / g), nw = (int)(new_freq / g);
   // torchaudio _get_sinc_resample_kernel (sinc_interp_hann, lowpass_filter_width 6, rolloff 0.99), float64
+  const RsGeometry geo = rs_geometry(orig_freq, new_freq);
+  const int orig = geo.orig, nw = geo.nw, width = geo.width, K = geo.K;
   const int lpw = 6;
-  const double rolloff = 0.99;
-  const double base = (double)(orig < nw ? orig : nw) * rolloff;
-  const int width = (int)ceil(lpw * (double)orig / base);
-  const int K = 2 * width + orig;
+  const double base = geo.base;
   SAD_REQUIRE((int64_t)K * nw * 4 <= (256ll << 20),
               "resample ratio too irregular: the polyphase table would exceed 256 MiB");
   std::vector<float> kt((size_t)K * nw);
@@ -291,6 +472,79 @@ extern "C" int sad_window_absmax_run(const float* wav, int64_t n, int64_t window
   SAD_REQUIRE(wav && out, "null pointer");
   hipLaunchKernelGGL(window_absmax_kernel, dim3((unsigned)n_windows), dim3(256), 0, (hipStream_t)stream, wav, n,
                      window, hop, out);
+  SAD_CHECK_HIP(hipGetLastError());
+  return SAD_OK;
+}
+
+// ---- trainer ingestion ---------------------------------------------------------
+extern "C" int sad_train_ingest_need_frames(int32_t orig_freq, int32_t new_freq, int64_t seg_len, int64_t* need) {
+  SAD_REQUIRE(need, "null need");
+  SAD_REQUIRE(orig_freq > 0 && new_freq > 0, "sample rates must be positive");
+  SAD_REQUIRE(seg_len > 0 && seg_len <= (1ll << 28), "seg_len must be in [1, 2^28]");
+  if (orig_freq == new_freq) {
+    *need = 2 * seg_len;
+    return SAD_OK;
+  }
+  // the last of the 2 seg_len outputs, m = j new + p, reads inputs up to j orig + K - 1 - width
+  const RsGeometry q = rs_geometry(orig_freq, new_freq);
+  *need = (2 * seg_len - 1) / q.nw * q.orig + q.orig + q.width;
+  return SAD_OK;
+}
+
+extern "C" int sad_train_ingest_file_tiles(int32_t orig_freq, int32_t new_freq, int64_t total_frames,
+                                           int64_t seg_len, int64_t* n_tiles) {
+  SAD_REQUIRE(n_tiles, "null n_tiles");
+  SAD_REQUIRE(orig_freq > 0 && new_freq > 0, "sample rates must be positive");
+  SAD_REQUIRE(seg_len > 0 && seg_len <= (1ll << 28), "seg_len must be in [1, 2^28]");
+  SAD_REQUIRE(total_frames >= 0 && total_frames <= (1ll << 40), "total_frames must be in [0, 2^40]");
+  const RsGeometry q = rs_geometry(orig_freq, new_freq);
+  const int64_t t = ti_file_tiles(orig_freq == new_freq, q, total_frames, seg_len);
+  SAD_REQUIRE(t > 0, "sample rate not supported by the batched kernel: few phases and a long input span");
+  *n_tiles = t;
+  return SAD_OK;
+}
+
+extern "C" int sad_train_ingest_run(const void* arena, int64_t arena_bytes, const int64_t* file_table,
+                                    const int64_t* d_file_table, int64_t n_files, const int32_t* d_tiles,
+                                    int64_t n_tiles, const sad_resample_plan* const* rate_plans, int32_t n_rates,
+                                    int64_t seg_len, float* out, void* stream) {
+  SAD_REQUIRE(seg_len > 0 && seg_len <= (1ll << 28), "seg_len must be in [1, 2^28]");
+  SAD_REQUIRE(n_files >= 0 && n_files <= (1 << 20), "n_files must be in [0, 2^20]");
+  SAD_REQUIRE(n_rates >= 1 && n_rates <= TI_MAX_RATES, "n_rates must be in [1, 8]");
+  SAD_REQUIRE(arena_bytes >= 0, "arena_bytes < 0");
+  if (n_files == 0) return SAD_OK;
+  SAD_REQUIRE(arena && file_table && d_file_table && d_tiles && rate_plans && out, "null pointer");
+  TrainRates rates = {};
+  RsGeometry geo[TI_MAX_RATES] = {};
+  for (int r = 0; r < n_rates; ++r) {
+    const sad_resample_plan* p = rate_plans[r];  // nullptr: the target rate
+    if (!p) continue;
+    rates.kt[r] = p->d_kt;
+    geo[r].orig = rates.orig[r] = p->orig;
+    geo[r].nw = rates.nw[r] = p->nw;
+    geo[r].width = rates.width[r] = p->width;
+    geo[r].K = rates.K[r] = p->K;
+  }
+  int64_t tiles = 0;
+  for (int64_t f = 0; f < n_files; ++f) {
+    const int64_t* t = file_table + f * TI_COLS;
+    const int64_t off = t[0], n_read = t[1], total = t[2], ch = t[3], enc = t[4], ri = t[5];
+    SAD_REQUIRE(ch >= 1 && ch <= 64, "file table: channels must be in [1, 64]");
+    SAD_REQUIRE(enc == SAD_PCM_I16 || enc == SAD_PCM_F32, "file table: encoding must be SAD_PCM_I16 or SAD_PCM_F32");
+    SAD_REQUIRE(ri >= 0 && ri < n_rates, "file table: rate index out of range");
+    SAD_REQUIRE(total >= 0 && total <= (1ll << 40) && n_read >= 0 && n_read <= total,
+                "file table: frames read / total frames");
+    SAD_REQUIRE(off >= 0 && off % 16 == 0, "file table: a file must start at a multiple of 16 bytes");
+    const int64_t bytes = n_read * ch * (enc == SAD_PCM_I16 ? 2 : 4);
+    SAD_REQUIRE(off <= arena_bytes && bytes <= arena_bytes - off, "file table: a file lies past the end of the arena");
+    const int64_t ft = ti_file_tiles(rate_plans[ri] == nullptr, geo[ri], total, seg_len);
+    SAD_REQUIRE(ft > 0, "sample rate not supported by the batched kernel: few phases and a long input span");
+    tiles += ft;
+  }
+  SAD_REQUIRE(n_tiles == tiles, "n_tiles is not the sum of the files' tile counts (sad_train_ingest_file_tiles)");
+  SAD_REQUIRE(tiles < (1ll << 31), "too many tiles for one launch");
+  hipLaunchKernelGGL(train_ingest_kernel, dim3((unsigned)tiles), dim3(256), 0, (hipStream_t)stream,
+                     (const unsigned char*)arena, d_file_table, (int)n_files, d_tiles, rates, seg_len, out);
   SAD_CHECK_HIP(hipGetLastError());
   return SAD_OK;
 }

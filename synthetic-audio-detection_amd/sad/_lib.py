@@ -74,6 +74,10 @@ SIGNATURES = {
     'sad_resample_out_len': (ctypes.c_int, [P, I64, ctypes.POINTER(I64)]),
     'sad_resample_run': (ctypes.c_int, [P, P, I64, P, I64, P]),
     'sad_window_absmax_run': (ctypes.c_int, [P, I64, I64, I64, I64, P, P]),
+    # trainer ingestion (include/sad.h "trainer ingestion")
+    'sad_train_ingest_need_frames': (ctypes.c_int, [I32, I32, I64, ctypes.POINTER(I64)]),
+    'sad_train_ingest_file_tiles': (ctypes.c_int, [I32, I32, I64, I64, ctypes.POINTER(I64)]),
+    'sad_train_ingest_run': (ctypes.c_int, [P, I64, P, P, I64, P, I64, FPP, I32, I64, P, P]),
     # catalogue scan (include/sad.h "catalogue scan")
     'sad_scan_select_workspace_size': (ctypes.c_int, [I64, I64, ctypes.POINTER(SZ)]),
     'sad_scan_select_run': (ctypes.c_int, [P, I64, P, P, I64, I64, I64, ctypes.c_float, I64, P, P, P, SZ, P]),

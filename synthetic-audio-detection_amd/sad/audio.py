@@ -70,17 +70,27 @@ def _wav_layout(path: str):
     return fmt, data_off, min(data_size, end - data_off)
 
 
-def read_wav(path: str):
-    """WAV -> (interleaved samples [frames * channels], channels, sample_rate).
-    16-bit PCM stays int16 as stored (the device scales it, sad_pcm_mono_run),
-    read straight from the file into one array; every other encoding is
-    decoded to float32 with torchaudio.load's normalize=True scaling."""
+def wav_header(path: str):
+    """The header walk of read_wav without the samples ->
+    (frames, channels, sample_rate, format tag, bits, data offset)."""
     fmt, off, size = _wav_layout(path)
     tag, ch, sr, _, _, bits = struct.unpack('<HHIIHH', fmt[:16])
     if tag == 0xFFFE and len(fmt) >= 26:  # WAVE_FORMAT_EXTENSIBLE: sub-format GUID's first 2 bytes
         tag = struct.unpack('<H', fmt[24:26])[0]
+    return size // ((bits // 8) * ch), ch, sr, tag, bits, off
+
+
+def read_wav(path: str, max_frames: int | None = None):
+    """WAV -> (interleaved samples [frames * channels], channels, sample_rate).
+    16-bit PCM stays int16 as stored (the device scales it, sad_pcm_mono_run),
+    read straight from the file into one array; every other encoding is
+    decoded to float32 with torchaudio.load's normalize=True scaling.
+    With max_frames only the first min(frames, max_frames) frames are read and
+    decoded (the trainer's device ingestion); the default reads the whole file."""
+    n, ch, sr, tag, bits, off = wav_header(path)
     width = bits // 8
-    n = size // (width * ch)
+    if max_frames is not None:
+        n = min(n, max(int(max_frames), 0))
     if tag == 1 and bits == 16:
         return np.fromfile(path, '<i2', count=n * ch, offset=off), ch, sr
     with open(path, 'rb') as f:

@@ -14,10 +14,15 @@ libsad (csrc/ingest.hip, include/sad.h "ingestion"):
 
 The host work left is the WAV header parse and the keep/skip decision over the
 per-window maxima (the same fp32 comparison as ``piece.abs().max() < thr``).
+
+The trainer's batched twin is at the end of the module ("trainer ingestion"):
+stored samples of a whole batch -> the [2B, seg_len] training segments in one
+upload and one launch (``TrainIngest``, ``collate_stored``).
 """
 from __future__ import annotations
 
 import ctypes
+import math
 from typing import List, Tuple
 
 import numpy as np
@@ -162,3 +167,196 @@ class Windows:
 
     def __len__(self):
         return len(self.starts)
+
+
+# ------------------------------------------------------------ trainer ingestion
+# The trainer's second input path (submodel_trainer.py --device-ingest): the
+# DataLoader workers read only the head of each file that the two 4 s training
+# segments need, as stored; one upload per batch carries the samples and the
+# tables; one launch (sad_train_ingest_run, csrc/ingest.hip) turns them into the
+# [2B, seg_len] fp32 segments TrainFrontEnd takes.  Everything up to the upload
+# is numpy / torch on the host and never loads libsad, so it runs in workers.
+TRAIN_TILE = 1024      # TI_TILE: outputs per tile (native and per-output forms)
+TRAIN_SPAN = 8192      # TI_SPAN: the per-output form's input span in LDS
+TRAIN_MAX_RATES = 8    # TI_MAX_RATES: distinct source rates in one launch
+TRAIN_COLS = 6         # file table columns (include/sad.h "trainer ingestion")
+TRAIN_WIDE_FRAMES = 64  # RS_WAVES * RS_R: frames per tile of the wide form
+
+
+def resample_geometry(sr: int, target_sr: int = 32000):
+    """(orig, new, width, K) of sad_resample_plan_create: the rates reduced by
+    their gcd, torchaudio's filter half-width and the taps per output."""
+    g = math.gcd(int(sr), int(target_sr))
+    orig, new = int(sr) // g, int(target_sr) // g
+    width = math.ceil(6 * orig / (min(orig, new) * 0.99))
+    return orig, new, width, 2 * width + orig
+
+
+def train_out_len(frames: int, sr: int, target_sr: int = 32000) -> int:
+    """The file's length at target_sr: ceil(new * frames / orig) (sad_resample_out_len)."""
+    if int(sr) == int(target_sr):
+        return int(frames)
+    orig, new, _, _ = resample_geometry(sr, target_sr)
+    return (new * int(frames) + orig - 1) // orig
+
+
+def train_need_frames(sr: int, seg_len: int, target_sr: int = 32000) -> int:
+    """sad_train_ingest_need_frames: the frames the first 2 seg_len output
+    samples read.  The last of them, m = 2 seg_len - 1 = j new + p, reads
+    inputs up to j orig + K - 1 - width = j orig + orig + width - 1."""
+    if int(sr) == int(target_sr):
+        return 2 * int(seg_len)
+    orig, new, width, _ = resample_geometry(sr, target_sr)
+    return (2 * int(seg_len) - 1) // new * orig + orig + width
+
+
+def train_segment_rule(n: int, seg_len: int, min_length_ratio: float = 0.9):
+    """segment_waveform's decision (submodel_trainer.py:155-187) from the 32 kHz
+    length alone: 'two' segments, the 'first' one twice, the zero-'pad'ded
+    file twice, or None (too short)."""
+    if n >= 2 * seg_len:
+        return 'two'
+    if n >= seg_len:
+        return 'first'
+    if n >= seg_len * min_length_ratio:
+        return 'pad'
+    return None
+
+
+def train_file_tiles(sr: int, total_frames: int, seg_len: int, target_sr: int = 32000) -> int:
+    """sad_train_ingest_file_tiles: workgroups of one file (0: the rate is refused)."""
+    n_out = train_out_len(total_frames, sr, target_sr)
+    m = seg_len if n_out < 2 * seg_len else 2 * seg_len
+    if int(sr) == int(target_sr):
+        return -(-m // TRAIN_TILE)
+    orig, new, _, K = resample_geometry(sr, target_sr)
+    if new < 64:
+        if ((TRAIN_TILE - 1) // new + 1) * orig + K > TRAIN_SPAN:
+            return 0
+        return -(-m // TRAIN_TILE)
+    return -(-(-(-m // new)) // TRAIN_WIDE_FRAMES) * (-(-new // 64))
+
+
+def train_rate_supported(sr: int, target_sr: int = 32000) -> bool:
+    return sr > 0 and train_file_tiles(sr, 1, 1, target_sr) > 0
+
+
+class StoredFile:
+    """One training file as its DataLoader worker leaves it: the first
+    `frames_read` frames as stored (int16, or fp32 decoded from another
+    encoding), the header's metadata, the label and the augmentation rows."""
+    __slots__ = ('samples', 'frames_read', 'frames', 'channels', 'sr', 'target', 'aug')
+
+    def __init__(self, samples: np.ndarray, frames: int, channels: int, sr: int, target: int, aug: torch.Tensor):
+        assert samples.dtype in (np.int16, np.float32) and samples.ndim == 1
+        self.samples, self.frames, self.channels, self.sr = samples, int(frames), int(channels), int(sr)
+        self.frames_read = samples.shape[0] // self.channels
+        self.target, self.aug = int(target), aug
+
+
+class StoredBatch:
+    """A batch of stored files, ready for one upload.  `arena` (uint8) holds the
+    files' samples, each starting at a multiple of 16 bytes, then the file
+    table [n_files, 6] int64 and the tile table [n_tiles, 2] int32
+    (include/sad.h "trainer ingestion").  `rates[i]` is the sample rate behind
+    rate index i; targets int64 [B]; aug int32 [B, 2, 8]."""
+
+    def __init__(self, arena, n_files, n_tiles, table_off, tiles_off, rates, targets, aug, seg_len):
+        self.arena, self.n_files, self.n_tiles = arena, int(n_files), int(n_tiles)
+        self.table_off, self.tiles_off = int(table_off), int(tiles_off)
+        self.rates, self.targets, self.aug, self.seg_len = tuple(rates), targets, aug, int(seg_len)
+
+    @property
+    def table(self) -> torch.Tensor:
+        return self.arena[self.table_off:self.table_off + 8 * TRAIN_COLS * self.n_files].view(torch.int64).view(
+            self.n_files, TRAIN_COLS)
+
+    @property
+    def tiles(self) -> torch.Tensor:
+        return self.arena[self.tiles_off:self.tiles_off + 8 * self.n_tiles].view(torch.int32).view(self.n_tiles, 2)
+
+    def pin_memory(self):
+        """DataLoader(pin_memory=True) calls this: the arena is the upload."""
+        self.arena = self.arena.pin_memory()
+        return self
+
+    def __len__(self):
+        return self.n_files
+
+
+def _align(n: int, a: int = 16) -> int:
+    return -(-n // a) * a
+
+
+def collate_stored(files, seg_len: int = 128000, target_sr: int = 32000):
+    """Collate for the stored-sample dataset: drops None (as custom_collate_fn
+    does), packs the rest into one StoredBatch, or returns None."""
+    files = [f for f in files if f is not None]
+    if not files:
+        return None
+    rates = []
+    for f in files:
+        if f.sr not in rates:
+            rates.append(f.sr)
+    if len(rates) > TRAIN_MAX_RATES:
+        raise ValueError(f'{len(rates)} distinct sample rates in one batch (at most {TRAIN_MAX_RATES})')
+    table = np.zeros((len(files), TRAIN_COLS), np.int64)
+    tiles, off = [], 0
+    for i, f in enumerate(files):
+        nt = train_file_tiles(f.sr, f.frames, seg_len, target_sr)
+        if nt <= 0:
+            raise ValueError(f'sample rate {f.sr} Hz is not supported by the batched ingestion kernel')
+        table[i] = (off, f.frames_read, f.frames, f.channels,
+                    _lib.SAD_PCM_I16 if f.samples.dtype == np.int16 else _lib.SAD_PCM_F32, rates.index(f.sr))
+        tiles.append(np.stack((np.full(nt, i, np.int32), np.arange(nt, dtype=np.int32)), axis=1))
+        off = _align(off + f.samples.nbytes)
+    tiles = np.concatenate(tiles)
+    table_off = off
+    tiles_off = _align(table_off + table.nbytes)
+    buf = np.zeros(_align(tiles_off + tiles.nbytes), np.uint8)
+    for row, f in zip(table, files):
+        buf[row[0]:row[0] + f.samples.nbytes] = f.samples.view(np.uint8)
+    buf[table_off:table_off + table.nbytes] = table.reshape(-1).view(np.uint8)
+    buf[tiles_off:tiles_off + tiles.nbytes] = tiles.reshape(-1).view(np.uint8)
+    return StoredBatch(torch.from_numpy(buf), len(files), tiles.shape[0], table_off, tiles_off, rates,
+                       torch.tensor([f.target for f in files]), torch.stack([f.aug for f in files]), seg_len)
+
+
+class TrainIngest:
+    """StoredBatch -> the batch's training segments on the device, fp32
+    [2B, seg_len] with file f's two segments in rows 2f and 2f + 1: one upload
+    and one launch per batch, queued on the current stream."""
+
+    def __init__(self, device='cuda', target_sr: int = 32000):
+        self.device = _dev(device)
+        self.target_sr = int(target_sr)
+
+    def need_frames(self, sr: int, seg_len: int) -> int:
+        n = _lib.I64()
+        _lib.call('sad_train_ingest_need_frames', int(sr), self.target_sr, int(seg_len), ctypes.byref(n))
+        return n.value
+
+    def file_tiles(self, sr: int, total_frames: int, seg_len: int) -> int:
+        n = _lib.I64()
+        _lib.call('sad_train_ingest_file_tiles', int(sr), self.target_sr, int(total_frames), int(seg_len),
+                  ctypes.byref(n))
+        return n.value
+
+    def __call__(self, batch: StoredBatch) -> torch.Tensor:
+        dev = self.device
+        plans = (ctypes.c_void_p * len(batch.rates))(*[
+            None if sr == self.target_sr else resampler(sr, self.target_sr, dev)._plan for sr in batch.rates])
+        d_arena = batch.arena.to(dev, non_blocking=True)  # pinned by the DataLoader: asynchronous
+        out = torch.empty(2 * batch.n_files, batch.seg_len, device=dev, dtype=torch.float32)
+        base = d_arena.data_ptr()
+        with torch.cuda.device(dev):
+            _lib.call('sad_train_ingest_run', base, batch.table_off, batch.table.data_ptr(), base + batch.table_off,
+                      batch.n_files, base + batch.tiles_off, batch.n_tiles, plans, len(batch.rates), batch.seg_len,
+                      _lib.ptr(out), _lib.stream_handle(dev))
+        return out
+
+    def segments(self, batch: StoredBatch) -> torch.Tensor:
+        """The rows in the host path's order: every file's first segment, then
+        every file's second (DeviceModel.images' torch.cat((input1, input2)))."""
+        out = self(batch)
+        return out.view(batch.n_files, 2, batch.seg_len).transpose(0, 1).reshape(2 * batch.n_files, batch.seg_len)

@@ -44,6 +44,18 @@ Differences (documented in DESIGN.md / INTEGRATION.md):
     mode on the inference plan's trunk entry; sub-models trained on one trunk
     and merged with ``model_merger.py --keep-backbone`` run it once at
     inference).
+  * ``--device-ingest`` (off by default): a second input path.  The default
+    path reads, decodes and resamples every whole file in a DataLoader worker
+    and ships 2 x 128,000 fp32 values per file through the loader's queue; with
+    the flag, ``StoredSampleDataset`` decides the segment rule from the WAV
+    header, reads only the frames the two segments need, as stored,
+    ``stored_collate_fn`` packs the batch into one byte arena with its file and
+    tile tables, and ``sad.ingest.TrainIngest`` turns it into the same
+    [2B, 128000] tensor with one upload and one launch (csrc/ingest.hip,
+    sad_train_ingest_run).  Same files, segments and augmentation draws;
+    an extension over the host path: 2-64 channel files are mixed to mono as
+    the inference path does instead of being skipped.  Its workers come from a
+    fork server and persist across epochs (get_dataloaders says why).
   * TensorBoard is optional (not installed here): scalars are logged instead.
 """
 from __future__ import annotations
@@ -109,6 +121,13 @@ def parse_args(argv=None):
                         help='trainer checkpoint whose conv1, bn1 and layer1-3 (parameters and BN statistics) are '
                              'loaded after the seeded init and stay frozen in eval mode; layer4 and the head train as '
                              'usual.  resnet18 with --precision bf16 or fp32 only')
+    parser.add_argument('--device-ingest', action='store_true',
+                        help='second input path: the DataLoader workers read only the frames of each file that the '
+                             'two 4 s segments need, as stored (int16 stays int16); one upload and one kernel launch '
+                             'per batch do the mono mix, the resampling to 32 kHz and the segment cut on the device.  '
+                             'Same segments and augmentation draws as the default host path (bit-identical for '
+                             '32 kHz mono files).  An extension over the host path: files of 2-64 channels are mixed '
+                             'to mono as the inference path does, where the host path skips them with a warning')
     args = parser.parse_args(argv)
     if args.trunk:
         if args.model_name != 'resnet18':
@@ -220,6 +239,49 @@ class SpectrogramDataset(Dataset):
         return len(self.samples)
 
 
+class StoredSampleDataset(SpectrogramDataset):
+    """``--device-ingest``: the same files, labels, segment rule and
+    augmentation draws as SpectrogramDataset, but __getitem__ decides from the
+    WAV header alone, reads only the frames the two segments need, as stored,
+    and returns a ``sad.ingest.StoredFile`` (or None); the device resamples
+    and cuts the segments (``sad.ingest.TrainIngest``).  Unlike the host path
+    it takes files of 1-64 channels (mixed to mono as the inference path does)."""
+
+    def __getitem__(self, index):
+        from sad import ingest as _ingest
+        path, target = self.samples[index]
+        try:
+            frames, channels, sample_rate, _, _, _ = _audio.wav_header(path)
+            if frames == 0:
+                logging.debug(f"Empty waveform detected at index {index} for path {path}")
+                return None
+            if not 1 <= channels <= 64:
+                raise ValueError(f'expected 1-64 channels, got {channels}')
+            if not _ingest.train_rate_supported(sample_rate, 32000):
+                raise ValueError(f'sample rate {sample_rate} Hz is not supported by the device ingestion')
+            n = _ingest.train_out_len(frames, sample_rate, 32000)
+            if _ingest.train_segment_rule(n, SEGMENT_LENGTH, self.min_length_ratio) is None:
+                logging.debug(f"File too short at index {index}, path {path}. Length: {n}, "
+                              f"Required: {2 * SEGMENT_LENGTH}")
+                return None
+            need = _ingest.train_need_frames(sample_rate, SEGMENT_LENGTH, 32000)
+            samples, _, _ = _audio.read_wav(path, max_frames=min(frames, need))
+            if samples.shape[0] != min(frames, need) * channels:
+                raise ValueError('the data chunk is shorter than its header says')
+            aug = self._aug_params()
+            return _ingest.StoredFile(samples, frames, channels, sample_rate, target, aug)
+        except Exception as e:
+            logging.warning(f"Error processing file at index {index}, path {path}: {str(e)}")
+            return None
+
+
+def stored_collate_fn(batch):
+    """``--device-ingest``: drops None samples as custom_collate_fn does; the
+    rest become one ``sad.ingest.StoredBatch`` (one byte arena + tables) or None."""
+    from sad import ingest as _ingest
+    return _ingest.collate_stored(batch, SEGMENT_LENGTH, 32000)
+
+
 def custom_collate_fn(batch):
     """Drops None samples (:221-238); returns (wave1 [B,T], target1, wave2,
     target2, aug [B,2,8]) or None."""
@@ -259,21 +321,30 @@ class DeviceModel:
     def __init__(self, trainer, frontend, rank=0, world=1, group=None):
         self.trainer, self.frontend = trainer, frontend
         self.rank, self.world, self.group = rank, world, group
+        self._ingest = None  # sad.ingest.TrainIngest, made when the first StoredBatch arrives
+
+    def _waves(self, batch):
+        """(waves [2B, 128000] fp32 on the device, targets [2B], aug [B, 2, 8]) of
+        either batch type, rows in the order first segments, second segments."""
+        from sad import ingest as _ingest
+        if isinstance(batch, _ingest.StoredBatch):  # --device-ingest
+            if self._ingest is None:
+                self._ingest = _ingest.TrainIngest(self.trainer.device)
+            return self._ingest.segments(batch), torch.cat((batch.targets, batch.targets), dim=0), batch.aug
+        input1, target1, input2, target2, aug = batch
+        waves = torch.cat((input1, input2), dim=0).to(self.trainer.device, non_blocking=True)
+        return waves, torch.cat((target1, target2), dim=0), aug
 
     def images(self, batch, train: bool):
-        input1, target1, input2, target2, aug = batch
-        dev = self.trainer.device
-        waves = torch.cat((input1, input2), dim=0).to(dev, non_blocking=True)
-        targets = torch.cat((target1, target2), dim=0)
+        waves, targets, aug = self._waves(batch)
         aug = torch.cat((aug[:, 0], aug[:, 1]), dim=0)
         masks = aug[:, :4] if train else None
         boxes = aug[:, 4:] if train else None
         return self.frontend(waves, masks, boxes), targets
 
     def maps(self, batch):
-        input1, target1, input2, target2, _ = batch
-        waves = torch.cat((input1, input2), dim=0).to(self.trainer.device, non_blocking=True)
-        return self.frontend.maps(waves), torch.cat((target1, target2), dim=0)
+        waves, targets, _ = self._waves(batch)
+        return self.frontend.maps(waves), targets
 
 
 def _allreduce_sum(values, model):
@@ -426,10 +497,11 @@ def get_dataloaders(args, rank: int = 0, world: int = 1):
     """Creates data loaders for training and validation (:463-511).  With
     world > 1 each rank reads a disjoint shard (DistributedSampler) of
     ``--batch-size`` files per step."""
-    train_dataset = SpectrogramDataset(args.data_dir, 'train', transform='train',
-                                       class_names=[args.Class0, args.Class1])
-    val_dataset = SpectrogramDataset(args.data_dir, 'test', transform='val',
-                                     class_names=[args.Class0, args.Class1])
+    stored = getattr(args, 'device_ingest', False)
+    dataset_cls = StoredSampleDataset if stored else SpectrogramDataset
+    collate = stored_collate_fn if stored else custom_collate_fn
+    train_dataset = dataset_cls(args.data_dir, 'train', transform='train', class_names=[args.Class0, args.Class1])
+    val_dataset = dataset_cls(args.data_dir, 'test', transform='val', class_names=[args.Class0, args.Class1])
     per_rank = args.batch_size if world > 1 else (args.batch_size * args.num_gpus if args.num_gpus > 0
                                                    else args.batch_size)
     logging.info(f"Total batch size: {per_rank * world}")
@@ -438,10 +510,16 @@ def get_dataloaders(args, rank: int = 0, world: int = 1):
         from torch.utils.data.distributed import DistributedSampler
         tsamp = DistributedSampler(train_dataset, num_replicas=world, rank=rank, shuffle=True, seed=args.seed)
         vsamp = DistributedSampler(val_dataset, num_replicas=world, rank=rank, shuffle=False)
+    # --device-ingest: the workers come from a fork server and live across epochs.
+    # Children forked from the process that holds the GPU slow its uploads from
+    # pinned memory many times over for as long as they live, and a
+    # worker that only reads a few hundred KiB per file is not worth a start per
+    # epoch.  The host path keeps the DataLoader defaults it always had.
+    extra = dict(multiprocessing_context='forkserver', persistent_workers=True) if stored and args.workers > 0 else {}
     train_loader = DataLoader(train_dataset, batch_size=per_rank, num_workers=args.workers, pin_memory=True,
-                              shuffle=tsamp is None, sampler=tsamp, drop_last=False, collate_fn=custom_collate_fn)
+                              shuffle=tsamp is None, sampler=tsamp, drop_last=False, collate_fn=collate, **extra)
     val_loader = DataLoader(val_dataset, batch_size=per_rank, num_workers=args.workers, pin_memory=True,
-                            shuffle=False, sampler=vsamp, drop_last=False, collate_fn=custom_collate_fn)
+                            shuffle=False, sampler=vsamp, drop_last=False, collate_fn=collate, **extra)
     return train_loader, val_loader
 
 
