@@ -454,8 +454,30 @@ int sad_heads_plan_create_dim(const float* const* params, int32_t n_heads, const
                               int32_t n_feat, int32_t feat_dim, sad_heads_plan** out);
 int sad_heads_plan_destroy(sad_heads_plan* plan);
 int sad_heads_workspace_size(const sad_heads_plan* plan, int64_t B, size_t* bytes);
-/* feats: n_feat pointers to [B,512] fp32; logits: [B, N, 2] fp32 (per head
- * [Real, Synthetic]); merged: [B, N+1] fp32 = [syn_1..syn_N, mean_i real_i]. */
+/* What sad_heads_merge_run will do with this plan: grouped = 1 when the second
+ * Linear of all heads runs as one grouped launch (the hidden columns are in
+ * head order: rank(h) == h below), 0 for one launch per head; row_range = the
+ * rows per GEMM launch (a larger B runs as several ranges). */
+int sad_heads_plan_info(const sad_heads_plan* plan, int32_t* grouped, int64_t* row_range);
+/* feats: n_feat pointers to [B, feat_dim] fp32 (the pointer of a feature group
+ * no head reads may be NULL); logits: [B, N, 2] fp32 (per head [Real,
+ * Synthetic]) or NULL; merged: [B, N+1] fp32 = [syn_1..syn_N, mean_i real_i].
+ * A short workspace or a NULL pointer of a used group is refused before any
+ * launch; a bad feat_dim or feat_index is refused by plan_create (a failed
+ * plan_create leaves nothing allocated).  Any B the workspace admits runs: the
+ * GEMMs take B as row ranges that keep their operands inside the 2 GiB buffer
+ * range (N = 6: 174,592 rows per range), and a row's value does not depend on
+ * its position in the batch.
+ *
+ * Workspace layout after a run, stable for tests (tests/test_gpu_heads.py
+ * reads the intermediate activations from it):
+ *   y1  [B][N*512] fp32 at the start: relu(bn1(Linear1(feats))).  Head h's 512
+ *       columns sit at 512 * rank(h), rank ordering the heads by
+ *       (feat_index[h], h): the heads of one backbone are neighbours, because
+ *       one GEMM per backbone writes them.
+ *   y2  [B][N*256] fp32 at float offset B*N*512: relu(bn2(Linear2(y1))), head h
+ *       at column 256 * h.
+ * The row ranges write into this one layout. */
 int sad_heads_merge_run(const sad_heads_plan* plan, const float* const* feats, int64_t B,
                         float* logits, float* merged, void* workspace, size_t ws_bytes,
                         void* stream);

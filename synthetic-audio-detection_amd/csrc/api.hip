@@ -936,12 +936,9 @@ extern "C" int sad_heads_plan_create(const float* const* params, int32_t n_heads
   return sad_heads_plan_create_dim(params, n_heads, feat_index, n_feat, 512, out);
 }
 
-extern "C" int sad_heads_plan_create_dim(const float* const* params, int32_t n_heads, const int32_t* feat_index,
-                                         int32_t n_feat, int32_t feat_dim, sad_heads_plan** out) {
-  SAD_REQUIRE(params && out && n_heads > 0 && n_feat > 0, "bad args");
-  SAD_REQUIRE(feat_dim > 0 && feat_dim % 64 == 0, "feat_dim must be a positive multiple of 64");
-  for (int i = 0; i < n_heads * 14; ++i) SAD_REQUIRE(params[i], "null head parameter");
-  auto* p = new sad_heads_plan();
+// Folds and uploads into *p; on an error the caller destroys p.
+static int heads_plan_fill(sad_heads_plan* p, const float* const* params, int n_heads, const int32_t* feat_index,
+                           int n_feat, int feat_dim) {
   p->n_heads = n_heads;
   p->n_feat = n_feat;
   p->feat_dim = feat_dim;
@@ -950,7 +947,6 @@ extern "C" int sad_heads_plan_create_dim(const float* const* params, int32_t n_h
   p->groups.assign(n_feat, {});
   for (int h = 0; h < n_heads; ++h) {
     const int f = feat_index ? feat_index[h] : 0;
-    SAD_REQUIRE(f >= 0 && f < n_feat, "feat_index out of range");
     p->feat_index.push_back(f);
     p->groups[f].push_back(h);
   }
@@ -971,14 +967,13 @@ extern "C" int sad_heads_plan_create_dim(const float* const* params, int32_t n_h
       p->y1_col[g[gi]] = col;
       col += 512;
     }
-    void* dw = nullptr;
-    void* db = nullptr;
+    // the plan owns each pointer from its allocation on (an empty group keeps NULL)
+    p->w1.push_back(nullptr);
+    p->b1.push_back(nullptr);
     if (!g.empty()) {
-      if ((rc = upload(&dw, w1))) return rc;
-      if ((rc = upload(&db, b1))) return rc;
+      if ((rc = upload((void**)&p->w1.back(), w1))) return rc;
+      if ((rc = upload((void**)&p->b1.back(), b1))) return rc;
     }
-    p->w1.push_back((float*)dw);
-    p->b1.push_back((float*)db);
   }
   std::vector<float> w2((size_t)n_heads * 256 * 512), b2(n_heads * 256), w3(n_heads * 512), b3(n_heads * 2);
   for (int h = 0; h < n_heads; ++h) {
@@ -995,6 +990,25 @@ extern "C" int sad_heads_plan_create_dim(const float* const* params, int32_t n_h
   if ((rc = upload((void**)&p->b2, b2))) return rc;
   if ((rc = upload((void**)&p->w3, w3))) return rc;
   if ((rc = upload((void**)&p->b3, b3))) return rc;
+  return SAD_OK;
+}
+
+extern "C" int sad_heads_plan_create_dim(const float* const* params, int32_t n_heads, const int32_t* feat_index,
+                                         int32_t n_feat, int32_t feat_dim, sad_heads_plan** out) {
+  SAD_REQUIRE(params && out && n_heads > 0 && n_feat > 0, "bad args");
+  SAD_REQUIRE(feat_dim > 0 && feat_dim % 64 == 0, "feat_dim must be a positive multiple of 64");
+  for (int i = 0; i < n_heads * 14; ++i) SAD_REQUIRE(params[i], "null head parameter");
+  for (int h = 0; h < n_heads; ++h)
+    SAD_REQUIRE(!feat_index || (feat_index[h] >= 0 && feat_index[h] < n_feat), "feat_index out of range");
+  // every head of one backbone shares the first GEMM: its weights are one operand
+  SAD_REQUIRE((int64_t)n_heads * 512 * feat_dim * 4 < (1ll << 31) && (int64_t)n_heads * 512 * 4 < (1ll << 31) - 64,
+              "too many heads for one GEMM operand (2 GiB buffer range)");
+  auto* p = new sad_heads_plan();
+  const int rc = heads_plan_fill(p, params, n_heads, feat_index, n_feat, feat_dim);
+  if (rc) {  // a failed upload: nothing of the half-built plan stays behind
+    sad_heads_plan_destroy(p);
+    return rc;
+  }
   *out = p;
   return SAD_OK;
 }
@@ -1017,6 +1031,30 @@ extern "C" int sad_heads_workspace_size(const sad_heads_plan* p, int64_t B, size
   return SAD_OK;
 }
 
+// The second layer is one grouped launch when the heads' hidden columns are in
+// head order (always for a shared backbone), otherwise one launch per head.
+static bool heads_regular(const sad_heads_plan* p) {
+  bool regular = true;
+  for (int h = 0; h < p->n_heads; ++h) regular = regular && p->y1_col[h] == h * 512;
+  return regular;
+}
+
+// Both GEMMs address their input with 32-bit byte offsets, so a batch runs as
+// row ranges that keep each operand inside launch_conv's buffer range: the
+// features are [rows][feat_dim], y1 is [rows][N*512] read 512 columns at a time.
+static int64_t heads_row_range(const sad_heads_plan* p) {
+  const int64_t range = std::min(conv_max_pixels(p->feat_dim, p->feat_dim, SAD_F32),
+                                 conv_max_pixels((int64_t)p->n_heads * 512, 512, SAD_F32));
+  return range >= 512 ? range - range % 512 : range;  // whole tiles of every variant
+}
+
+extern "C" int sad_heads_plan_info(const sad_heads_plan* p, int32_t* grouped, int64_t* row_range) {
+  SAD_REQUIRE(p && grouped && row_range, "null args");
+  *grouped = heads_regular(p) ? 1 : 0;
+  *row_range = heads_row_range(p);
+  return SAD_OK;
+}
+
 extern "C" int sad_heads_merge_run(const sad_heads_plan* p, const float* const* feats, int64_t B, float* logits,
                                    float* merged, void* ws, size_t ws_bytes, void* stream) {
   SAD_REQUIRE(p && feats && merged && ws, "null args");
@@ -1026,66 +1064,73 @@ extern "C" int sad_heads_merge_run(const sad_heads_plan* p, const float* const* 
     set_error("heads workspace too small");
     return SAD_ERR_NOMEM;
   }
+  // refusals come before the first launch: a used group's features must be there
+  for (int f = 0; f < p->n_feat; ++f) SAD_REQUIRE(p->groups[f].empty() || feats[f], "null feature pointer");
   if (B == 0) return SAD_OK;
   hipStream_t s = (hipStream_t)stream;
   const int N = p->n_heads;
   float* y1 = (float*)ws;
   float* y2 = y1 + (size_t)B * N * 512;
-  int rc, col = 0;
-  for (int f = 0; f < p->n_feat; ++f) {
-    const int G = (int)p->groups[f].size();
-    if (!G) continue;
-    SAD_REQUIRE(feats[f], "null feature pointer");
-    ConvArgs a{};
-    a.in = feats[f];
-    a.in_pstride = p->feat_dim;
-    a.N = (int)B;
-    a.H = a.W = 1;
-    a.Cin = p->feat_dim;
-    a.wt = p->w1[f];
-    a.bias = p->b1[f];
-    a.out = y1 + col;
-    a.out_pstride = (int64_t)N * 512;
-    a.Ho = a.Wo = 1;
-    a.Cout = 512 * G;
-    a.KH = a.KW = 1;
-    a.stride = 1;
-    a.pad = 0;
-    a.relu = 1;
-    a.M = B;
-    if ((rc = launch_conv(a, SAD_F32, s))) return rc;
-    col += 512 * G;
-  }
-  // the N heads' Linear(512, 256) + BN1d + ReLU: one grouped launch when the
-  // heads' hidden columns are in head order (always for a shared backbone)
-  bool regular = true;
-  for (int h = 0; h < N; ++h) regular = regular && p->y1_col[h] == h * 512;
-  for (int h = 0; h < (regular ? 1 : N); ++h) {
-    ConvArgs a{};
-    if (regular && N > 1) {
-      a.groups = N;
-      a.in_gstride = 512;
-      a.wt_gstride = (int64_t)256 * 512;
-      a.bias_gstride = 256;
-      a.out_gstride = 256;
+  // Rows are independent (a row's K order does not depend on its position) and
+  // every range writes its own rows of the one workspace layout (include/sad.h).
+  const int64_t range = heads_row_range(p);
+  SAD_REQUIRE(range >= 1, "heads: one row exceeds the 2 GiB buffer range");
+  const bool regular = heads_regular(p);
+  int rc;
+  for (int64_t r0 = 0; r0 < B; r0 += range) {
+    const int64_t rows = std::min(range, B - r0);
+    int col = 0;
+    for (int f = 0; f < p->n_feat; ++f) {
+      const int G = (int)p->groups[f].size();
+      if (!G) continue;
+      ConvArgs a{};
+      a.in = feats[f] + r0 * p->feat_dim;
+      a.in_pstride = p->feat_dim;
+      a.N = (int)rows;
+      a.H = a.W = 1;
+      a.Cin = p->feat_dim;
+      a.wt = p->w1[f];
+      a.bias = p->b1[f];
+      a.out = y1 + r0 * N * 512 + col;
+      a.out_pstride = (int64_t)N * 512;
+      a.Ho = a.Wo = 1;
+      a.Cout = 512 * G;
+      a.KH = a.KW = 1;
+      a.stride = 1;
+      a.pad = 0;
+      a.relu = 1;
+      a.M = rows;
+      if ((rc = launch_conv(a, SAD_F32, s))) return rc;
+      col += 512 * G;
     }
-    a.in = y1 + p->y1_col[h];
-    a.in_pstride = (int64_t)N * 512;
-    a.N = (int)B;
-    a.H = a.W = 1;
-    a.Cin = 512;
-    a.wt = p->w2 + (size_t)h * 256 * 512;
-    a.bias = p->b2 + h * 256;
-    a.out = y2 + h * 256;
-    a.out_pstride = (int64_t)N * 256;
-    a.Ho = a.Wo = 1;
-    a.Cout = 256;
-    a.KH = a.KW = 1;
-    a.stride = 1;
-    a.pad = 0;
-    a.relu = 1;
-    a.M = B;
-    if ((rc = launch_conv(a, SAD_F32, s))) return rc;
+    // the N heads' Linear(512, 256) + BN1d + ReLU (grouped or per head: heads_regular)
+    for (int h = 0; h < (regular ? 1 : N); ++h) {
+      ConvArgs a{};
+      if (regular && N > 1) {
+        a.groups = N;
+        a.in_gstride = 512;
+        a.wt_gstride = (int64_t)256 * 512;
+        a.bias_gstride = 256;
+        a.out_gstride = 256;
+      }
+      a.in = y1 + r0 * N * 512 + p->y1_col[h];
+      a.in_pstride = (int64_t)N * 512;
+      a.N = (int)rows;
+      a.H = a.W = 1;
+      a.Cin = 512;
+      a.wt = p->w2 + (size_t)h * 256 * 512;
+      a.bias = p->b2 + h * 256;
+      a.out = y2 + r0 * N * 256 + h * 256;
+      a.out_pstride = (int64_t)N * 256;
+      a.Ho = a.Wo = 1;
+      a.Cout = 256;
+      a.KH = a.KW = 1;
+      a.stride = 1;
+      a.pad = 0;
+      a.relu = 1;
+      a.M = rows;
+      if ((rc = launch_conv(a, SAD_F32, s))) return rc;
+    }
   }
   return launch_heads_final(y2, B, N, p->w3, p->b3, logits, merged, s);
 }

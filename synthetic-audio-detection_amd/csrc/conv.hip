@@ -1058,13 +1058,26 @@ static int launch_conv_v(const ConvArgs& a, int v, hipStream_t s) {
 
 int default_conv_variant(const ConvArgs& a) { return a.Cout % 128 == 0 ? 5 : 2; }
 
+// The input operand's addressable span and its limit (32-bit buffer offsets).
+constexpr int64_t CONV_IN_LIMIT = (1ll << 31) - 64;
+static int64_t conv_in_bytes(int64_t pixels, int64_t in_pstride, int Cin, int ES) {
+  return ((pixels - 1) * in_pstride + Cin) * ES;
+}
+
+int64_t conv_max_pixels(int64_t in_pstride, int Cin, int dtype) {
+  const int ES = dtype == SAD_BF16 ? 2 : 4;
+  // largest P with conv_in_bytes(P) < CONV_IN_LIMIT
+  const int64_t room = (CONV_IN_LIMIT - 1) / ES - Cin;
+  return room < 0 ? 0 : room / in_pstride + 1;
+}
+
 int launch_conv(const ConvArgs& a_in, int dtype, hipStream_t s, int variant) {
   const int EPC = dtype == SAD_BF16 ? 8 : 4;
   const int ES = dtype == SAD_BF16 ? 2 : 4;
   ConvArgs a = a_in;
-  a.in_bytes = (((int64_t)a.N * a.H * a.W - 1) * a.in_pstride + a.Cin) * ES;
+  a.in_bytes = conv_in_bytes((int64_t)a.N * a.H * a.W, a.in_pstride, a.Cin, ES);
   a.wt_bytes = (int64_t)a.Cout * a.KH * a.KW * a.Cin * ES;
-  SAD_REQUIRE(a.in_bytes < (1ll << 31) - 64 && a.wt_bytes < (1ll << 31),
+  SAD_REQUIRE(a.in_bytes < CONV_IN_LIMIT && a.wt_bytes < (1ll << 31),
               "conv operand exceeds the 2 GiB buffer range (lower the micro-batch)");
   SAD_REQUIRE(a.Cin % (8 * EPC) == 0, "Cin must be a multiple of the K-step");
   SAD_REQUIRE(a.Cout % 64 == 0, "Cout must be a multiple of 64");

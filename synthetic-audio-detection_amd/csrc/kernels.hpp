@@ -119,6 +119,9 @@ struct StemArgs {
 };
 
 int launch_conv(const ConvArgs& a, int dtype, hipStream_t s, int variant = 0);
+// most input pixels (N*H*W) launch_conv accepts at this pixel stride (elements):
+// the operand must stay inside the 2 GiB buffer range
+int64_t conv_max_pixels(int64_t in_pstride, int Cin, int dtype);
 int default_conv_variant(const ConvArgs& a);
 int launch_stem(const StemArgs& a, int dtype, hipStream_t s);
 // training stem (bf16): raw conv1 -> sign(gamma)-pooled raw maps + statistic partials

@@ -113,7 +113,8 @@ SIGNATURES = {
     'sad_heads_plan_create_dim': (ctypes.c_int, [FPP, I32, ctypes.POINTER(I32), I32, I32, ctypes.POINTER(P)]),
     'sad_heads_plan_destroy': (ctypes.c_int, [P]),
     'sad_heads_workspace_size': (ctypes.c_int, [P, I64, ctypes.POINTER(SZ)]),
-    'sad_heads_merge_run': (ctypes.c_int, [P, FPP, I64, P, P, P, SZ, P]),
+    'sad_heads_plan_info': (ctypes.c_int, [P, ctypes.POINTER(I32), ctypes.POINTER(I64)]),
+    'sad_heads_merge_run':(ctypes.c_int, [P, FPP, I64, P, P, P, SZ, P]),
     'sad_conv2d_run': (ctypes.c_int, [P, I64, I32, I32, I32, P, P, P, P, I32, I32, I32, I32, I32, I32, I32, P]),
     'sad_block_conv_run': (ctypes.c_int, [P, I64, I32, I32, I32, P, I32, I32, I32, I32, P, I32, P, P, P, I32, I32,
                                           I32, I32, I32, I32, I32, P]),

@@ -402,11 +402,38 @@ class Heads:
             _lib.call('sad_heads_plan_create_dim', _lib.pointer_array(arrays), self.n_heads, fi, n_feat,
                       feat_dim, _lib.ctypes.byref(self._plan))
         self.n_feat = n_feat
+        self.feat_dim = feat_dim
+        self._used = sorted(set(int(f) for f in feat_index))
         self._ws = None
+
+    def _check_feats(self, feats) -> int:
+        """The C entry reads raw pointers as [B, feat_dim] fp32 rows on the
+        plan's device, so anything else must fail here.  An entry of a feature
+        group no head reads may be None."""
+        if len(feats) != self.n_feat:
+            raise ValueError(f'expected {self.n_feat} feature tensors, got {len(feats)}')
+        B = None
+        for i, f in enumerate(feats):
+            if f is None:
+                if i in self._used:
+                    raise ValueError(f'features {i} are read by a head and must not be None')
+                continue
+            if f.dtype != torch.float32:
+                raise ValueError(f'features {i} must be float32 (got {f.dtype})')
+            if f.device != self.device:
+                raise ValueError(f'features {i} are on {f.device}, the plan is on {self.device}')
+            if f.dim() != 2 or f.shape[1] != self.feat_dim:
+                raise ValueError(f'features {i} must be [B, {self.feat_dim}] (got {tuple(f.shape)})')
+            if not f.is_contiguous():
+                raise ValueError(f'features {i} must be contiguous')
+            if B is not None and f.shape[0] != B:
+                raise ValueError(f'features {i} have {f.shape[0]} rows, the others {B}')
+            B = f.shape[0]
+        return B
 
     def __call__(self, feats: Sequence[torch.Tensor], logits: torch.Tensor | None = None,
                  merged: torch.Tensor | None = None):
-        B = feats[0].shape[0]
+        B = self._check_feats(feats)
         if logits is None:
             logits = torch.empty(B, self.n_heads, 2, device=self.device, dtype=torch.float32)
         if merged is None:
@@ -415,7 +442,7 @@ class Heads:
         _lib.call('sad_heads_workspace_size', self._plan, B, _lib.ctypes.byref(sz))
         if self._ws is None or self._ws.numel() < sz.value:
             self._ws = torch.empty(sz.value, dtype=torch.uint8, device=self.device)
-        fp = (_lib.ctypes.c_void_p * self.n_feat)(*[f.data_ptr() for f in feats])
+        fp = (_lib.ctypes.c_void_p * self.n_feat)(*[_lib.ptr(f) for f in feats])
         with torch.cuda.device(self.device):
             _lib.call('sad_heads_merge_run', self._plan, fp, B, _lib.ptr(logits), _lib.ptr(merged),
                       _lib.ptr(self._ws), self._ws.numel(), _lib.stream_handle(self.device))
