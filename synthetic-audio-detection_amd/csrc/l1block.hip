@@ -114,36 +114,8 @@ constexpr int l1b_k1(int u) { return u < SA * NF ? u % NF : (u - SA * NF) / NB1;
 }  // namespace l1b
 
 __device__ __forceinline__ int l1b_key(int x) { return (int)((l1b::KEY >> (3 * x)) & 7); }
-// LDS access by byte address (the lane constants below carry the LDS base, so
-// no base is added in front of a read; a constant added to `ad` becomes the
-// instruction's immediate offset)
-// T: a native vector type (l1b_v4, l1b_v2, f32x4) -- HIP's uint4 / uint2 are
-// structs, which the optimiser takes apart into 4-B accesses
-template <typename T>
-__device__ __forceinline__ T l1b_ld(int ad) {
-  return *(const __attribute__((address_space(3))) T*)(unsigned)ad;
-}
-template <typename T>
-__device__ __forceinline__ void l1b_st(int ad, const T& v) {
-  *(__attribute__((address_space(3))) T*)(unsigned)ad = v;
-}
-
-// One LDS-DMA piece (16 B per lane from buffer offset voff to LDS [dst + OFF +
-// 16 lane]) with M0 formed in the statement as a scalar base plus an
-// immediate, and the descriptor passed as one 128-bit scalar value.
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Winline-asm"
-template <int OFF>
-__device__ __forceinline__ void l1b_dma16(const l1b_v4& rsrc, int voff, unsigned dst) {
-  asm volatile(
-      "s_add_u32 m0, %1, %3\n\t"
-      "s_nop 0\n\t"
-      "buffer_load_dwordx4 %0, %2, 0 offen lds"
-      :
-      : "v"(voff), "s"(dst), "s"(rsrc), "n"(OFF)
-      : "memory", "m0", "scc");
-}
-#pragma clang diagnostic pop
+// (l1b_ld / l1b_st, LDS access by byte address, and l1b_dma16, one LDS-DMA
+// piece with a pinned descriptor, are in rwconv.hpp: l2conv.hip shares them)
 
 // AB: false = the production kernel, which holds no ablation code at all; true
 // = the timing-ablation form, which tests a.ablate at run time around the

@@ -1,7 +1,8 @@
 // rwconv.hpp -- helpers of the resident-weight conv kernels (l1block.hip,
 // l2conv.hip): weights held in AGPRs for a whole launch, so the MFMAs that read
 // them are inline asm (hipcc only places MFMA A/B operands in VGPRs); packed
-// bf16 conversion and ReLU; compile-time loops.
+// bf16 conversion and ReLU; LDS access by byte address and the LDS-DMA piece
+// with a pinned descriptor; compile-time loops.
 #pragma once
 #include <utility>
 
@@ -59,9 +60,47 @@ __device__ __forceinline__ uint32_t l1b_relu2(uint32_t x) {
   asm("v_pk_max_i16 %0, %1, 0" : "=v"(r) : "v"(x));
   return r;
 }
+// the same against a scalar floor per half: 0 = ReLU, 0x8000 (the least int16)
+// = none, so a conv whose ReLU is a launch argument decides it once, in an SGPR
+__device__ __forceinline__ uint32_t l1b_relu2s(uint32_t x, int floor2) {
+  uint32_t r;
+  asm("v_pk_max_i16 %0, %1, %2" : "=v"(r) : "v"(x), "s"(floor2));
+  return r;
+}
 __device__ __forceinline__ uint32_t l1b_pk(float lo, float hi) {
   return __builtin_bit_cast(uint32_t, __builtin_convertvector((l1b_f2){lo, hi}, l1b_bf2));
 }
+
+// LDS access by byte address (the kernels' lane constants carry the LDS base, so
+// no base is added in front of a read; a constant added to `ad` becomes the
+// instruction's immediate offset)
+// T: a native vector type (l1b_v4, l1b_v2, f32x4) -- HIP's uint4 / uint2 are
+// structs, which the optimiser takes apart into 4-B accesses
+template <typename T>
+__device__ __forceinline__ T l1b_ld(int ad) {
+  return *(const __attribute__((address_space(3))) T*)(unsigned)ad;
+}
+template <typename T>
+__device__ __forceinline__ void l1b_st(int ad, const T& v) {
+  *(__attribute__((address_space(3))) T*)(unsigned)ad = v;
+}
+
+// One LDS-DMA piece (16 B per lane from buffer offset voff to LDS [dst + OFF +
+// 16 lane]) with M0 formed in the statement as a scalar base plus an
+// immediate, and the descriptor passed as one 128-bit scalar value.
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Winline-asm"
+template <int OFF>
+__device__ __forceinline__ void l1b_dma16(const l1b_v4& rsrc, int voff, unsigned dst) {
+  asm volatile(
+      "s_add_u32 m0, %1, %3\n\t"
+      "s_nop 0\n\t"
+      "buffer_load_dwordx4 %0, %2, 0 offen lds"
+      :
+      : "v"(voff), "s"(dst), "s"(rsrc), "n"(OFF)
+      : "memory", "m0", "scc");
+}
+#pragma clang diagnostic pop
 
 template <typename F, int... I>
 __device__ __forceinline__ void l1b_for_impl(F&& f, std::integer_sequence<int, I...>) {
