@@ -16,56 +16,18 @@ namespace sad {
 static thread_local std::string g_err;
 void set_error(const std::string& msg) { g_err = msg; }
 
-// ResNet-18 conv table in timm state-dict order.
-struct ConvSpec {
-  int cin, cout, k, stride, pad;
-};
-static std::vector<ConvSpec> resnet18_specs() {
-  std::vector<ConvSpec> v;
-  v.push_back({3, 64, 7, 2, 3});  // conv1
-  int inp = 64;
-  const int planes[4] = {64, 128, 256, 512};
-  for (int li = 0; li < 4; ++li) {
-    for (int b = 0; b < 2; ++b) {
-      const int s = (b == 0 && li > 0) ? 2 : 1;
-      v.push_back({inp, planes[li], 3, s, 1});          // conv1
-      v.push_back({planes[li], planes[li], 3, 1, 1});   // conv2
-      if (b == 0 && (s != 1 || inp != planes[li])) v.push_back({inp, planes[li], 1, s, 0});  // downsample
-      inp = planes[li];
-    }
-  }
-  return v;
-}
-
-struct DevConv {
-  ConvSpec spec;
-  void* w = nullptr;      // [cout][k][k][cin] dtype
-  float* bias = nullptr;  // [cout]
-};
-
 }  // namespace sad
 
 using namespace sad;
-
-struct DevBlock {           // one BasicBlock on the block-conv path
-  int cin, cout, stride;
-  void* w1 = nullptr;        // conv1: [cout][9*cin]
-  float* b1 = nullptr;
-  void* w2 = nullptr;        // conv2 + shortcut: [cout][9*cout + cin_sc] (identity or downsample)
-  float* b2 = nullptr;
-  int cin_sc;
-};
 
 struct sad_backbone_plan {
   int dtype;
   int mh, mw;
   int device;
-  bool block_path;           // true: persistent block-conv kernels (shortcut in GEMM)
   void* stem_w = nullptr;
   float* stem_b = nullptr;
-  float* stem_w3 = nullptr;    // distinct-channel stem (sad_backbone_run_img3)
-  std::vector<DevConv> convs;  // index 1.. of the spec table (igemm path)
-  std::vector<DevBlock> blocks;
+  float* stem_w3 = nullptr;  // distinct-channel stem (sad_backbone_run_img3)
+  std::vector<BasicBlock> blocks;
 };
 
 struct sad_heads_plan {
@@ -193,92 +155,42 @@ int check_map_upsamples(int map_h, int map_w) {
 
 extern "C" int sad_backbone_plan_create(const float* const* params, int32_t n_params, int32_t dtype,
                                         int32_t map_h, int32_t map_w, sad_backbone_plan** out) {
-  const std::vector<ConvSpec> specs = resnet18_specs();
   SAD_REQUIRE(params && out, "null params/out");
-  SAD_REQUIRE(n_params == (int)specs.size() * 5, "n_params must be 100 (20 conv+BN groups)");
+  SAD_REQUIRE(n_params == 20 * 5, "n_params must be 100 (20 conv+BN groups)");
   SAD_REQUIRE(dtype == SAD_F32 || dtype == SAD_BF16 || dtype == SAD_BF16X3, "dtype");
   SAD_REQUIRE(map_h > 0 && map_w > 0, "map shape");
   if (int rc = check_map_upsamples(map_h, map_w)) return rc;
   for (int i = 0; i < n_params; ++i) SAD_REQUIRE(params[i] != nullptr, "null parameter pointer");
+  {
+    const char* env = getenv("SAD_BACKBONE_PATH");
+    SAD_REQUIRE(!(env && strcmp(env, "igemm") == 0),
+                "SAD_BACKBONE_PATH=igemm: the first-generation per-conv backbone path was removed (unset the variable)");
+  }
   auto* p = new sad_backbone_plan();
   p->dtype = dtype;
   p->mh = map_h;
   p->mw = map_w;
   (void)hipGetDevice(&p->device);
-  std::vector<double> sc, sh;
   int rc;
   if ((rc = fold_stem(params, dtype, &p->stem_w, &p->stem_b, &p->stem_w3))) {
     sad_backbone_plan_destroy(p);  // (no device: the first upload fails)
     return rc;
   }
-  // first-generation per-conv weights (SAD_BACKBONE_PATH=igemm; fp32 / bf16 only)
-  for (size_t ci = 1; ci < specs.size() && dtype != SAD_BF16X3; ++ci) {
-    const ConvSpec& s = specs[ci];
-    const float* W = params[ci * 5];
-    fold_bn(params[ci * 5 + 1], params[ci * 5 + 2], params[ci * 5 + 3], params[ci * 5 + 4], s.cout, sc, sh);
-    std::vector<double> w((size_t)s.cout * s.k * s.k * s.cin);
-    for (int co = 0; co < s.cout; ++co)
-      for (int c = 0; c < s.cin; ++c)
-        for (int ky = 0; ky < s.k; ++ky)
-          for (int kx = 0; kx < s.k; ++kx)
-            w[(((size_t)co * s.k + ky) * s.k + kx) * s.cin + c] =
-                (double)W[(((size_t)co * s.cin + c) * s.k + ky) * s.k + kx] * sc[co];
-    DevConv d;
-    d.spec = s;
-    if ((rc = upload_typed(&d.w, w, dtype))) return rc;
-    std::vector<float> bf(sh.begin(), sh.end());
-    if ((rc = upload((void**)&d.bias, bf))) return rc;
-    p->convs.push_back(d);
-  }
-  // block path: conv2 and the shortcut (identity or folded downsample) share one
-  // GEMM with a concatenated K axis; biases add.
-  {
-    const char* env = getenv("SAD_BACKBONE_PATH");
-    p->block_path = !(env && strcmp(env, "igemm") == 0) || dtype == SAD_BF16X3;
-    size_t ci = 1;
-    int inp = 64;
-    const int planes[4] = {64, 128, 256, 512};
-    for (int li = 0; li < 4; ++li) {
-      for (int b = 0; b < 2; ++b) {
-        const size_t i1 = ci++, i2 = ci++;
-        const bool has_ds = (b == 0 && li > 0);
-        const size_t ids = has_ds ? ci++ : 0;
-        const int co = planes[li];
-        DevBlock blk;
-        blk.cin = inp;
-        blk.cout = co;
-        blk.stride = has_ds ? 2 : 1;
-        blk.cin_sc = inp;
-        std::vector<double> sc1, sh1, sc2, sh2, scd, shd;
-        fold_bn(params[i1 * 5 + 1], params[i1 * 5 + 2], params[i1 * 5 + 3], params[i1 * 5 + 4], co, sc1, sh1);
-        fold_bn(params[i2 * 5 + 1], params[i2 * 5 + 2], params[i2 * 5 + 3], params[i2 * 5 + 4], co, sc2, sh2);
-        if (has_ds) fold_bn(params[ids * 5 + 1], params[ids * 5 + 2], params[ids * 5 + 3], params[ids * 5 + 4], co, scd, shd);
-        const int k1 = 9 * inp, k2 = 9 * co + inp;
-        std::vector<double> w1((size_t)co * k1), w2((size_t)co * k2, 0.0), b2(co);
-        const float* W1 = params[i1 * 5];
-        const float* W2 = params[i2 * 5];
-        for (int o = 0; o < co; ++o) {
-          for (int c = 0; c < inp; ++c)
-            for (int t = 0; t < 9; ++t) w1[(size_t)o * k1 + t * inp + c] = (double)W1[((size_t)o * inp + c) * 9 + t] * sc1[o];
-          for (int c = 0; c < co; ++c)
-            for (int t = 0; t < 9; ++t) w2[(size_t)o * k2 + t * co + c] = (double)W2[((size_t)o * co + c) * 9 + t] * sc2[o];
-          if (has_ds) {
-            const float* Wd = params[ids * 5];
-            for (int c = 0; c < inp; ++c) w2[(size_t)o * k2 + 9 * co + c] = (double)Wd[(size_t)o * inp + c] * scd[o];
-            b2[o] = sh2[o] + shd[o];
-          } else {
-            w2[(size_t)o * k2 + 9 * co + o] = 1.0;  // identity shortcut (exact in bf16)
-            b2[o] = sh2[o];
-          }
-        }
-        if ((rc = upload_typed(&blk.w1, w1, dtype, k1))) return rc;
-        if ((rc = upload_typed(&blk.w2, w2, dtype, k2))) return rc;
-        std::vector<float> b1f(sh1.begin(), sh1.end()), b2f(b2.begin(), b2.end());
-        if ((rc = upload((void**)&blk.b1, b1f))) return rc;
-        if ((rc = upload((void**)&blk.b2, b2f))) return rc;
-        p->blocks.push_back(blk);
-        inp = co;
+  // 20 conv+BN groups in timm state-dict order: the stem, then per block conv1,
+  // conv2 and (the first blocks of layers 2-4) the downsample
+  const float* const* q = params + 5;
+  int inp = 64;
+  for (int li = 0; li < 4; ++li) {
+    for (int b = 0; b < 2; ++b) {
+      const bool has_ds = b == 0 && li > 0;
+      p->blocks.emplace_back();
+      if ((rc = fold_basic_block(q, q + 5, has_ds ? q + 10 : nullptr, inp, 64 << li, has_ds ? 2 : 1, dtype,
+                                 p->blocks.back()))) {
+        sad_backbone_plan_destroy(p);
+        return rc;
       }
+      q += has_ds ? 15 : 10;
+      inp = 64 << li;
     }
   }
   *out = p;
@@ -290,16 +202,7 @@ extern "C" int sad_backbone_plan_destroy(sad_backbone_plan* p) {
   (void)hipFree(p->stem_w);
   (void)hipFree(p->stem_b);
   (void)hipFree(p->stem_w3);
-  for (auto& c : p->convs) {
-    (void)hipFree(c.w);
-    (void)hipFree(c.bias);
-  }
-  for (auto& b : p->blocks) {
-    (void)hipFree(b.w1);
-    (void)hipFree(b.b1);
-    (void)hipFree(b.w2);
-    (void)hipFree(b.b2);
-  }
+  for (auto& b : p->blocks) free_basic_block(b);
   delete p;
   return SAD_OK;
 }
@@ -329,7 +232,7 @@ static std::mutex g_prof_mu;
 static bool g_prof_on = false;
 static std::vector<ProfRec> g_prof;
 
-static int timed_block_conv(const BlockConvArgs& a, int dtype, hipStream_t s, double flops) {
+int sad::timed_block_conv(const BlockConvArgs& a, int dtype, hipStream_t s, double flops) {
   if (!g_prof_on) return launch_block_conv(a, dtype, s);
   ProfRec r{default_block_variant(a, dtype), flops, nullptr, nullptr, 0};
   SAD_CHECK_HIP(hipEventCreate(&r.e0));
@@ -348,13 +251,10 @@ static int timed_block_conv(const BlockConvArgs& a, int dtype, hipStream_t s, do
 // the fused BasicBlock kernel (variant 40; A/B switch).  Same box, 2 rounds:
 // fused with 128-segment front sub-batches 52.5k seg/s vs 51.5k unfused at 32
 bool sad::l1_fused() {
-  static const bool v = [] {
-    const char* e = getenv("SAD_L1_FUSED");
-    return e ? atoi(e) != 0 : true;
-  }();
+  static const bool v = env_int("SAD_L1_FUSED", 1) != 0;
   return v;
 }
-static int timed_l1block(const L1BlockArgs& a, hipStream_t s, double flops) {
+int sad::timed_l1block(const L1BlockArgs& a, hipStream_t s, double flops) {
   if (!g_prof_on) return launch_l1block(a, s);
   ProfRec r{40, flops, nullptr, nullptr, 1};
   SAD_CHECK_HIP(hipEventCreate(&r.e0));
@@ -418,97 +318,21 @@ extern "C" int sad_profile_end(int32_t variant, double* total_ms, int64_t* launc
   return SAD_OK;
 }
 
-// Blocks [b0, b1) of the block path on n segments: *in (NHWC, H x H x C) ->
-// *in (the last output; the buffers *in, *alt, tmp rotate).
+// Blocks [b0, b1) on n segments: *in (NHWC, H x H x C) -> *in (the last
+// output; the buffers *in and *alt swap per block, tmp holds conv1's output).
 // pool_out (optional): fuse the global average pool into the last block's conv2
 // when its kernel can (*pooled says whether it did; its NHWC output is not written)
 static int run_blocks(const sad_backbone_plan* p, size_t b0, size_t b1, int64_t n, void** in, void** alt, void* tmp,
                       int& H, int& C, hipStream_t s, float* pool_out = nullptr, bool* pooled = nullptr) {
-  int rc;
-  void* bufA = *in;
-  void* bufB = *alt;
-  void* bufT = tmp;
-  const int64_t mb = n;
-  {
-    for (size_t bi = b0; bi < b1; ++bi) {
-      const DevBlock& blk = p->blocks[bi];
-      const int Ho = H / blk.stride;
-      if (p->dtype == SAD_BF16 && blk.stride == 1 && blk.cout == 64 && C == 64 && blk.cin == 64 && H % 16 == 0 &&
-          l1_fused()) {
-        // layer1: the whole BasicBlock as one kernel (variant 40)
-        L1BlockArgs f{};
-        f.x = (const u16*)bufA;
-        f.out = (u16*)bufB;
-        f.N = (int)mb;
-        f.H = f.W = H;
-        f.w1 = (const u16*)blk.w1;
-        f.w1_ld = 9 * 64;
-        f.b1 = blk.b1;
-        f.w2 = (const u16*)blk.w2;
-        f.w2_ld = 9 * 64 + blk.cin_sc;  // (the identity's K columns are not read)
-        f.b2 = blk.b2;
-        if ((rc = timed_l1block(f, s, 2.0 * 2.0 * mb * H * H * 64 * 576.0))) return rc;
-        std::swap(bufA, bufB);
-        continue;
-      }
-      BlockConvArgs a{};
-      a.in0 = bufA;
-      a.in0_pstride = C;
-      a.N = (int)mb;
-      a.H = a.W = H;
-      a.Cin = C;
-      a.KH = a.KW = 3;
-      a.stride = blk.stride;
-      a.pad = 1;
-      a.wt = blk.w1;
-      a.bias = blk.b1;
-      a.out = bufT;
-      a.out_pstride = blk.cout;
-      a.Ho = a.Wo = Ho;
-      a.Cout = blk.cout;
-      a.relu = 1;
-      a.M = mb * Ho * Ho;
-      if ((rc = timed_block_conv(a, p->dtype, s, 2.0 * a.M * a.Cout * 9.0 * C))) return rc;
-      BlockConvArgs b2 = a;
-      b2.in0 = bufT;
-      b2.in0_pstride = blk.cout;
-      b2.H = b2.W = Ho;
-      b2.Cin = blk.cout;
-      b2.stride = 1;
-      b2.wt_ld = 9 * blk.cout + blk.cin_sc;
-      if ((p->dtype == SAD_BF16 || p->dtype == SAD_BF16X3) && blk.stride == 1 && Ho % 16 == 0 &&
-          (blk.cout <= 64 || (blk.cout <= 128 && layer2_halo() && !(p->dtype == SAD_BF16 && layer2_v31()) &&
-                            !(p->dtype == SAD_BF16X3 && x3_layer2_v31())) ||
-           v31_identity_residual(p->dtype, blk.cout, Ho))) {
-        // identity blocks of layer1/2: the shortcut is an epilogue add on the halo kernel;
-        // bf16 layer3/4: on variant 31 (w2 keeps its layout: the identity's K columns are not read)
-        b2.res = bufA;
-        b2.res_pstride = C;
-      } else {
-        b2.in1 = bufA;
-        b2.in1_pstride = C;
-        b2.H1 = b2.W1 = H;
-        b2.Cin1 = C;
-        b2.ss1 = blk.stride;
-      }
-      b2.wt = blk.w2;
-      b2.bias = blk.b2;
-      b2.out = bufB;
-      // algorithmic work: conv2, plus the 1x1 downsample when there is one (not the identity)
-      if (pool_out && bi + 1 == b1 && block_conv_can_pool(b2, p->dtype)) {
-        b2.pool_out = pool_out;
-        b2.out = nullptr;
-        *pooled = true;
-      }
-      const double fl2 = 2.0 * b2.M * b2.Cout * (9.0 * blk.cout + (blk.stride != 1 ? (double)C : 0.0));
-      if ((rc = timed_block_conv(b2, p->dtype, s, fl2))) return rc;
-      std::swap(bufA, bufB);
-      H = Ho;
-      C = blk.cout;
-    }
+  for (size_t bi = b0; bi < b1; ++bi) {
+    const BasicBlock& blk = p->blocks[bi];
+    if (int rc = run_basic_block(blk, p->dtype, *in, tmp, *alt, n, H, s, bi + 1 == b1 ? pool_out : nullptr, pooled,
+                                 true))
+      return rc;
+    std::swap(*in, *alt);
+    H /= blk.stride;
+    C = blk.cout;
   }
-  *in = bufA;
-  *alt = bufB;
   return SAD_OK;
 }
 
@@ -529,10 +353,7 @@ static int run_blocks(const sad_backbone_plan* p, size_t b0, size_t b1, int64_t 
 // (same box, 3 rounds, tools/r03_sweep2.sh: 59.0-59.1k vs 57.3-58.9k seg/s;
 // 512 with micro-batch 2048 within 0.2 % of 256).
 static int front_sub_batch(int dtype) {
-  static int v = [] {
-    const char* e = getenv("SAD_FRONT_MB");
-    return e ? atoi(e) : -1;
-  }();
+  static int v = env_int("SAD_FRONT_MB", -1);
   if (v >= 0) return v;
   // split-bf16 (layer1 on variant 42): 64, +0.8 % over 32 in the parity mode
   // (same box, 2 rounds; 128 and the whole micro-batch are slower,
@@ -575,88 +396,6 @@ static int run_front(const sad_backbone_plan* p, const float* map, const float* 
   return SAD_OK;
 }
 
-// BasicBlocks [b0, b1) of the first-generation per-conv path (fp32 / bf16):
-// *in -> *in (the last output; *in and *alt swap per block, tmp holds conv1's
-// output and dsbuf the downsample's).
-static int run_convs(const sad_backbone_plan* p, size_t b0, size_t b1, int64_t mb, void** in, void** alt, void* tmp,
-                     void* dsbuf, int& H, int& C, hipStream_t s) {
-  int rc;
-  void* bufA = *in;
-  void* bufB = *alt;
-  void* bufT = tmp;
-  void* bufD = dsbuf;
-  size_t ci = 0;
-  for (size_t bi = 0; bi < b0; ++bi) ci += (bi % 2 == 0 && bi >= 2) ? 3 : 2;
-  for (size_t bi = b0; bi < b1; ++bi) {
-    const DevConv& c1 = p->convs[ci++];
-    const DevConv& c2 = p->convs[ci++];
-    const DevConv* ds = nullptr;
-    if (bi % 2 == 0 && bi >= 2) ds = &p->convs[ci++];
-    const int Ho = H / c1.spec.stride;
-    ConvArgs a{};
-    a.in = bufA;
-    a.in_pstride = C;
-    a.N = (int)mb;
-    a.H = H;
-    a.W = H;
-    a.Cin = C;
-    a.wt = c1.w;
-    a.bias = c1.bias;
-    a.res = nullptr;
-    a.out = bufT;
-    a.out_pstride = c1.spec.cout;
-    a.Ho = Ho;
-    a.Wo = Ho;
-    a.Cout = c1.spec.cout;
-    a.KH = a.KW = c1.spec.k;
-    a.stride = c1.spec.stride;
-    a.pad = c1.spec.pad;
-    a.relu = 1;
-    a.M = mb * Ho * Ho;
-    if ((rc = launch_conv(a, p->dtype, s))) return rc;
-    const void* res = bufA;
-    if (ds) {
-      ConvArgs d = a;
-      d.wt = ds->w;
-      d.bias = ds->bias;
-      d.out = bufD;
-      d.KH = d.KW = 1;
-      d.pad = 0;
-      d.relu = 0;
-      if ((rc = launch_conv(d, p->dtype, s))) return rc;
-      res = bufD;
-    }
-    ConvArgs a2{};
-    a2.in = bufT;
-    a2.in_pstride = c2.spec.cin;
-    a2.N = (int)mb;
-    a2.H = Ho;
-    a2.W = Ho;
-    a2.Cin = c2.spec.cin;
-    a2.wt = c2.w;
-    a2.bias = c2.bias;
-    a2.res = res;
-    a2.res_pstride = c2.spec.cout;
-    a2.out = bufB;
-    a2.out_pstride = c2.spec.cout;
-    a2.Ho = Ho;
-    a2.Wo = Ho;
-    a2.Cout = c2.spec.cout;
-    a2.KH = a2.KW = 3;
-    a2.stride = 1;
-    a2.pad = 1;
-    a2.relu = 1;
-    a2.M = mb * Ho * Ho;
-    if ((rc = launch_conv(a2, p->dtype, s))) return rc;
-    std::swap(bufA, bufB);
-    H = Ho;
-    C = c2.spec.cout;
-  }
-  *in = bufA;
-  *alt = bufB;
-  return SAD_OK;
-}
-
 static int run_chunk(const sad_backbone_plan* p, const float* map, const float* img, int64_t mb, float* feats,
                      void* layer4_out, char* ws, hipStream_t s, const float* img3 = nullptr) {
   const size_t ab = act_bytes(p, mb);
@@ -667,19 +406,12 @@ static int run_chunk(const sad_backbone_plan* p, const float* map, const float* 
   int rc;
   int H = 128, C = 64;
   bool pooled = false;  // the last conv wrote the pooled features itself
-  if (p->block_path) {
-    if ((rc = run_front(p, map, img, img3, mb, bufA, bufB, bufT, bufD, H, C, s))) return rc;
-    void* a0 = bufD;
-    void* a1 = bufA;
-    if ((rc = run_blocks(p, 2, p->blocks.size(), mb, &a0, &a1, bufB, H, C, s, layer4_out ? nullptr : feats,
-                         &pooled)))
-      return rc;
-    bufA = a0;
-  } else {
-    StemArgs st{map, img, p->mh, p->mw, p->stem_w, p->stem_b, bufA, mb, img3, p->stem_w3};
-    if ((rc = launch_stem(st, p->dtype, s))) return rc;
-    if ((rc = run_convs(p, 0, 8, mb, &bufA, &bufB, bufT, bufD, H, C, s))) return rc;
-  }
+  if ((rc = run_front(p, map, img, img3, mb, bufA, bufB, bufT, bufD, H, C, s))) return rc;
+  void* a0 = bufD;
+  void* a1 = bufA;
+  if ((rc = run_blocks(p, 2, p->blocks.size(), mb, &a0, &a1, bufB, H, C, s, layer4_out ? nullptr : feats, &pooled)))
+    return rc;
+  bufA = a0;
   if (layer4_out) {
     const size_t es = p->dtype == SAD_BF16 ? 2 : 4;
     SAD_CHECK_HIP(hipMemcpyAsync(layer4_out, bufA, (size_t)mb * H * H * C * es, hipMemcpyDeviceToDevice, s));
@@ -707,23 +439,14 @@ static int trunk_chunk(const sad_backbone_plan* p, const float* map, const float
   void* bufD = ws + 3 * ab;
   int rc;
   int H = 128, C = 64;
-  void* src;
+  if ((rc = run_front(p, map, img, nullptr, mb, bufA, bufB, bufT, bufD, H, C, s))) return rc;
+  void* a0 = bufD;
+  void* a1 = bufA;
+  if ((rc = run_blocks(p, 2, 5, mb, &a0, &a1, bufB, H, C, s))) return rc;
+  // layer3's second block writes straight into l3_out
+  void* src = a0;
   void* dst = l3_out;
-  if (p->block_path) {
-    if ((rc = run_front(p, map, img, nullptr, mb, bufA, bufB, bufT, bufD, H, C, s))) return rc;
-    void* a0 = bufD;
-    void* a1 = bufA;
-    if ((rc = run_blocks(p, 2, 5, mb, &a0, &a1, bufB, H, C, s))) return rc;
-    // layer3's second block writes straight into l3_out
-    src = a0;
-    if ((rc = run_blocks(p, 5, 6, mb, &src, &dst, bufB, H, C, s))) return rc;
-  } else {
-    StemArgs st{map, img, p->mh, p->mw, p->stem_w, p->stem_b, bufA, mb, nullptr, p->stem_w3};
-    if ((rc = launch_stem(st, p->dtype, s))) return rc;
-    if ((rc = run_convs(p, 0, 5, mb, &bufA, &bufB, bufT, bufD, H, C, s))) return rc;
-    src = bufA;
-    if ((rc = run_convs(p, 5, 6, mb, &src, &dst, bufT, bufD, H, C, s))) return rc;
-  }
+  if ((rc = run_blocks(p, 5, 6, mb, &src, &dst, bufB, H, C, s))) return rc;
   if (src != l3_out || H != 32 || C != 256) {
     set_error("internal: layer3 output not in l3_out");
     return SAD_ERR_STATE;
@@ -740,21 +463,14 @@ static int tail_chunk(const sad_backbone_plan* p, const void* l3, int64_t mb, fl
   void* bufX = ws;
   void* bufY = ws + ab;
   void* bufT = ws + 2 * ab;
-  void* bufD = ws + 3 * ab;
   int rc;
   int H = 32, C = 256;
   bool pooled = false;
   void* src = const_cast<void*>(l3);
   void* dst = bufX;
-  if (p->block_path) {
-    if ((rc = run_blocks(p, 6, 7, mb, &src, &dst, bufT, H, C, s))) return rc;
-    dst = bufY;
-    if ((rc = run_blocks(p, 7, 8, mb, &src, &dst, bufT, H, C, s, feats, &pooled))) return rc;
-  } else {
-    if ((rc = run_convs(p, 6, 7, mb, &src, &dst, bufT, bufD, H, C, s))) return rc;
-    dst = bufY;
-    if ((rc = run_convs(p, 7, 8, mb, &src, &dst, bufT, bufD, H, C, s))) return rc;
-  }
+  if ((rc = run_blocks(p, 6, 7, mb, &src, &dst, bufT, H, C, s))) return rc;
+  dst = bufY;
+  if ((rc = run_blocks(p, 7, 8, mb, &src, &dst, bufT, H, C, s, feats, &pooled))) return rc;
   if (pooled) return SAD_OK;
   if (src != bufY) {
     set_error("internal: layer4 output not in its workspace buffer");
@@ -825,7 +541,6 @@ extern "C" int sad_backbone_shared_run(const sad_backbone_plan* trunk, const sad
     SAD_REQUIRE(tails[t]->blocks.size() == 8, "tail is not a ResNet-18 plan");
     SAD_REQUIRE(tails[t]->dtype == trunk->dtype, "tail plan dtype differs from the trunk's");
     SAD_REQUIRE(tails[t]->mh == trunk->mh && tails[t]->mw == trunk->mw, "tail plan map size differs from the trunk's");
-    SAD_REQUIRE(tails[t]->block_path == trunk->block_path, "tail plan path differs from the trunk's");
   }
   size_t need = 0;
   sad_backbone_shared_workspace_size(trunk, mb, &need);

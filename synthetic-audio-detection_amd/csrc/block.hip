@@ -758,11 +758,8 @@ static bool halo_ok(const BlockConvArgs& a, int dtype) {
 // 2.2-2.7 % slower end to end (same box, 3 rounds: 52.4k vs 53.7k seg/s): at
 // 128 channels a K-step is half the MFMAs for the same per-step weight loads,
 // waits and chunk barriers.  Off by default; tested (test_gpu_blockconv.py).
-bool layer2_v31() {
-  static const bool v = [] {
-    const char* e = getenv("SAD_L2_V31");
-    return e ? atoi(e) != 0 : false;
-  }();
+static bool layer2_v31() {
+  static const bool v = env_int("SAD_L2_V31", 0) != 0;
   return v;
 }
 // variant 31's contract (either tile width): 3x3/s1/p1, 16 x 16 tiles, whole
@@ -778,29 +775,20 @@ static bool halo31_ok(const BlockConvArgs& a, int dtype) {
 // downsample, layer2.1's two; identity / downsample as shortcut columns) on
 // variant 31's split form with 128-channel tiles instead of the weight-ring
 // halo kernel (variant 20) and the implicit GEMM (variant 15)
-bool x3_layer2_v31() {
-  static const bool v = [] {
-    const char* e = getenv("SAD_X3_L2_V31");
-    return e ? atoi(e) != 0 : true;
-  }();
+static bool x3_layer2_v31() {
+  static const bool v = env_int("SAD_X3_L2_V31", 1) != 0;
   return v;
 }
 // SAD_L2_RW=0 runs layer2's second block on the weight-ring halo kernel
 // (variant 20) instead of the resident-weight conv (variant 41; A/B switch)
 static bool l2_rw() {
-  static const bool v = [] {
-    const char* e = getenv("SAD_L2_RW");
-    return e ? atoi(e) != 0 : true;
-  }();
+  static const bool v = env_int("SAD_L2_RW", 1) != 0;
   return v;
 }
 // SAD_L2_DS_RW=0 runs layer2.0's conv2 + downsample on the implicit GEMM
 // (variant 15) instead of variant 41's downsample form (A/B switch)
 static bool l2_ds_rw() {
-  static const bool v = [] {
-    const char* e = getenv("SAD_L2_DS_RW");
-    return e ? atoi(e) != 0 : true;
-  }();
+  static const bool v = env_int("SAD_L2_DS_RW", 1) != 0;
   return v;
 }
 // variant 41's downsample form: 128 -> 128 3x3/s1/p1 + 1x1/2 of a 64-channel
@@ -828,10 +816,7 @@ static bool l2conv_ds_ok(const BlockConvArgs& a) {
 // 552 vs 553; end to end +0.2 % (2 of 3 same-box rounds,
 // profiles/r05_s2_ab.log).  SAD_S2_PATCH=1 keeps variant 32.
 static int s2_patch() {
-  static const int v = [] {
-    const char* e = getenv("SAD_S2_PATCH");
-    return e ? atoi(e) : 2;
-  }();
+  static const int v = env_int("SAD_S2_PATCH", 2);
   return v;
 }
 // SAD_X3_S2 (split-bf16): 44 (default) runs layer3/4's stride-2 convs on
@@ -840,20 +825,14 @@ static int s2_patch() {
 // (Cout 128) ties (1,071 vs 1,066) and stays on the GEMM; end to end neutral
 // (profiles/r05_s2_ab.log), kept for the bytes (1.2 vs 1.8-1.9 GB per launch).
 static int x3_s2_variant() {
-  static const int v = [] {
-    const char* e = getenv("SAD_X3_S2");
-    return e ? atoi(e) : 44;
-  }();
+  static const int v = env_int("SAD_X3_S2", 44);
   return v;
 }
 // SAD_L2S2_RW=0 runs layer2.0's stride-2 conv1 (64 -> 128) on the implicit
 // GEMM (variant 15) instead of the resident-weight stride-2 conv (variant 43,
 // l2s2conv.hip; A/B switch)
 static bool l2s2_rw() {
-  static const bool v = [] {
-    const char* e = getenv("SAD_L2S2_RW");
-    return e ? atoi(e) != 0 : true;
-  }();
+  static const bool v = env_int("SAD_L2S2_RW", 1) != 0;
   return v;
 }
 // variant 43's contract: 64 -> 128 3x3/s2/p1, output tiles 16 x 16, input
@@ -863,11 +842,8 @@ static bool l2s2_ok(const BlockConvArgs& a) {
   return a.KH == 3 && a.KW == 3 && a.stride == 2 && a.pad == 1 && a.Cin == 64 && a.Cout == 128 && a.Ho % 16 == 0 &&
          a.Wo % 16 == 0 && a.H == 2 * a.Ho && a.W == 2 * a.Wo && !a.in1 && !a.res && !a.pool_out;
 }
-bool layer2_halo() {
-  static const bool v = [] {
-    const char* e = getenv("SAD_L2_HALO");
-    return e ? atoi(e) != 0 : true;
-  }();
+static bool layer2_halo() {
+  static const bool v = env_int("SAD_L2_HALO", 1) != 0;
   return v;
 }
 // SAD_C128_VARIANT: block-conv variant for Cout = 128 GEMM convs (layer2's first
@@ -875,20 +851,14 @@ bool layer2_halo() {
 // waves, 2 workgroups/CU): l2.c1 580 -> 473 us in isolation at mb 512, +0.5 %
 // end-to-end same-box (gpurun_out/ab_c128.log)
 static int c128_variant() {
-  static const int v = [] {
-    const char* e = getenv("SAD_C128_VARIANT");
-    return e ? atoi(e) : 15;
-  }();
+  static const int v = env_int("SAD_C128_VARIANT", 15);
   return v;
 }
 // SAD_HALO_C128: halo variant for the Cout = 128 stride-1 convs (layer2's second
 // block): 20 (64-channel tiles, two workgroups per tile) or 22 (128-channel
 // tiles, 64 x 64 wave tiles, register epilogue); A/B switch
 static int halo_c128_variant() {
-  static const int v = [] {
-    const char* e = getenv("SAD_HALO_C128");
-    return e ? atoi(e) : 20;
-  }();
+  static const int v = env_int("SAD_HALO_C128", 20);
   return v;
 }
 // SAD_X3_L1 (split-bf16 layer1, A/B): 42 = the resident-weight conv of layer2's
@@ -896,18 +866,12 @@ static int halo_c128_variant() {
 // 64 logical channels per workgroup, 3 MFMAs per fragment read), 26 = round 2's
 // half-the-channels kernel (weights in LDS)
 static int x3_l1_variant() {
-  static const int v = [] {
-    const char* e = getenv("SAD_X3_L1");
-    return e ? atoi(e) : 42;
-  }();
+  static const int v = env_int("SAD_X3_L1", 42);
   return v;
 }
 // SAD_X3_RW=0 runs split-bf16 layer1 on the weight-ring halo kernel (variant 20) instead of variant 26 (A/B)
 static bool x3_rw() {
-  static const bool v = [] {
-    const char* e = getenv("SAD_X3_RW");
-    return e ? atoi(e) != 0 : true;
-  }();
+  static const bool v = env_int("SAD_X3_RW", 1) != 0;
   return v;
 }
 // The stride-1 3x3 convs with Cout % 256 == 0 (layer3/4): bf16 runs the
@@ -920,25 +884,39 @@ static bool x3_rw() {
 // parity mode over variant 31's, same box, 2 rounds, profiles/
 // r04_x3_halo256_ab.log) or 31; SAD_HALO256=0 still puts both modes on variant 13
 static int x3_halo256_variant() {
-  static const int v = [] {
-    const char* e = getenv("SAD_X3_HALO256");
-    return e ? atoi(e) : 30;
-  }();
+  static const int v = env_int("SAD_X3_HALO256", 30);
   return v;
 }
 static int halo256_mode() {
-  static const int v = [] {
-    const char* e = getenv("SAD_HALO256");
-    return e ? atoi(e) : 2;
-  }();
+  static const int v = env_int("SAD_HALO256", 2);
   return v;
 }
 // bf16 identity blocks of layer3/4 (Cout a multiple of 256, 16 x 16 tiles):
 // the shortcut goes to variant 31 as an epilogue residual, as layer1/2's goes
 // to their kernels, when variant 31 runs these convs at all (SAD_HALO256 = 2,
 // the default; 0 / 1 keep the identity as K columns on variants 13 / 30)
-bool v31_identity_residual(int dtype, int cout, int Ho) {
+static bool v31_identity_residual(int dtype, int cout, int Ho) {
   return dtype == SAD_BF16 && halo256_mode() == 2 && cout % 256 == 0 && Ho % 16 == 0;
+}
+// Does conv2 of this identity BasicBlock take its shortcut as the epilogue
+// residual `res` (true) or as identity K columns over `in1` (false)?  The
+// callers' form has to be the one the variant default_block_variant then picks
+// reads: bf16 and split-bf16, stride 1, no downsample, 16 x 16 tiles, and
+//   Cout <= 64 (layer1): variants 25 (bf16) and 42 / 26 / 20 (split-bf16) add `res`;
+//   Cout <= 128 (layer2): variants 41 / 20 add `res`, unless SAD_L2_HALO=0 (the
+//     implicit GEMM, A/B) or variant 31's 128-channel tiles run these convs
+//     (SAD_L2_V31=1; split-bf16: SAD_X3_L2_V31, the default), which take K columns;
+//   Cout % 256 == 0 (layer3/4), bf16 only: variant 31 adds `res` in fp32 to its
+//     accumulators (the split-bf16 variants 30 / 31 take K columns).
+// The four-product plans (x4) run every conv on the implicit GEMM: K columns.
+// The weights keep their layout either way: with `res` the identity's K columns
+// are not read.
+bool identity_shortcut_is_res(int dtype, int x4, int cin, int cout, int stride, bool has_ds, int Ho) {
+  if (x4 || !(dtype == SAD_BF16 || dtype == SAD_BF16X3) || stride != 1 || has_ds || cin != cout || Ho % 16 != 0)
+    return false;
+  return cout <= 64 || (cout <= 128 && layer2_halo() && !(dtype == SAD_BF16 && layer2_v31()) &&
+                        !(dtype == SAD_BF16X3 && x3_layer2_v31())) ||
+         v31_identity_residual(dtype, cout, Ho);
 }
 static int block_device_cus() {
   static int cus[64] = {};
@@ -978,7 +956,7 @@ int default_block_variant(const BlockConvArgs& a, int dtype) {
   // layer2's 128-channel stride-1 convs (incl. conv2 + downsample / identity as
   // shortcut columns): variant 31 with 128-channel tiles
   if (dtype == SAD_BF16 && layer2_v31() && a.Cout == 128 && !a.res && halo31_ok(a, dtype)) return 31;
-  // layer3/4's identity blocks (run_blocks, resnet.hip's identity_epilogue):
+  // layer3/4's identity blocks (identity_shortcut_is_res):
   // variant 31 with the shortcut as an epilogue residual -- before the halo
   // kernel's line below, and whatever the batch size (see the layer3/4 choice)
   if (dtype == SAD_BF16 && halo256_mode() == 2 && a.res && a.Cout % 256 == 0 && halo31_ok(a, dtype)) return 31;
@@ -1041,10 +1019,7 @@ constexpr size_t kStampWords = SAD_CLOCK_BASE + 4 * SAD_CLOCK_WGS;
 // SAD_STAMP_EVERY=n: stamp only every n-th launch of a stamped variant (the
 // others run unstamped and unsynchronised, so a loop keeps the chip loaded)
 static bool stamp_this_launch(int which) {  // counted per stamped variant
-  static const int every = [] {
-    const char* e = getenv("SAD_STAMP_EVERY");
-    return e ? std::max(1, atoi(e)) : 1;
-  }();
+  static const int every = std::max(1, env_int("SAD_STAMP_EVERY", 1));
   static long count[2] = {0, 0};
   return count[which]++ % every == every - 1;
 }

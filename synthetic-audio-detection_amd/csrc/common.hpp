@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
 #include <string.h>
 #include <string>
 
@@ -32,6 +33,12 @@ void set_error(const std::string& msg);
       return SAD_ERR_ARG;                                                          \
     }                                                                              \
   } while (0)
+
+// an integer A/B switch from the environment (callers keep the value in a static)
+inline int env_int(const char* name, int dflt) {
+  const char* e = getenv(name);
+  return e ? atoi(e) : dflt;
+}
 
 // host fp32 -> bf16 round-to-nearest-even (no NaN inputs on this path)
 inline u16 f2bf_host(float f) {

@@ -841,10 +841,7 @@ struct sad_frontend_plan : sad::FrontendPlan {};
 // agent-scope release / acquire fences; 2 fused, the tiles stored and re-read
 // at agent scope (sc1) with no cache write-back / invalidate
 static int fe_fused() {
-  static const int v = [] {
-    const char* e = getenv("SAD_FE_FUSED");
-    return e ? atoi(e) : 0;
-  }();
+  static const int v = env_int("SAD_FE_FUSED", 0);
   return v;
 }
 
@@ -917,8 +914,7 @@ static int frontend_plan_build(const sad_frontend_cfg* cfg, const float* fb_in, 
     const int nA = std::min(cfg->n_mels, 64);
     int ml[2] = {0, 0};
     std::vector<int> lane_d(128, 0);
-    const char* me = getenv("SAD_FE_MATCH");  // 0: round 4's greedy split (A/B)
-    const bool match = !(me && atoi(me) == 0);
+    const bool match = env_int("SAD_FE_MATCH", 1) != 0;  // 0: round 4's greedy split (A/B)
     for (int q = 0; q < 2; ++q) {
       std::vector<int> rows(q == 0 ? ord.begin() : ord.begin() + nA, q == 0 ? ord.begin() + nA : ord.end());
       for (int m : rows) ml[q] = std::max(ml[q], ln[m]);
@@ -1075,20 +1071,14 @@ extern "C" int sad_frontend_frames(const sad_frontend_plan* p, int32_t* n) {
 
 // SAD_FE_XCD_MAP=1: the XCD-aware block order (a segment's blocks on one XCD)
 static int fe_xcd_map() {
-  static const int v = [] {
-    const char* e = getenv("SAD_FE_XCD_MAP");
-    return e ? atoi(e) : 0;
-  }();
+  static const int v = env_int("SAD_FE_XCD_MAP", 0);
   return v;
 }
 
 // SAD_FE_FM (default 1): the frame-major form (three workgroups per CU; see
 // fe_mel_db_kernel); 0: the staged form (dB rows through LDS, two per CU)
 static int fe_fm() {
-  static const int v = [] {
-    const char* e = getenv("SAD_FE_FM");
-    return e ? atoi(e) : 1;
-  }();
+  static const int v = env_int("SAD_FE_FM", 1);
   return v;
 }
 

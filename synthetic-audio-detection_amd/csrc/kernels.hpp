@@ -130,11 +130,9 @@ constexpr int STEM_TRAIN_PARTS = 16;  // statistic partials per image (128 poole
 int launch_block_conv(const BlockConvArgs& a, int dtype, hipStream_t s, int variant = 0);
 int default_block_variant(const BlockConvArgs& a, int dtype);
 int gemm_block_variant(const BlockConvArgs& a);  // default_block_variant without 30/31 (bf16)
-bool layer2_halo();
-bool x3_layer2_v31();  // SAD_X3_L2_V31 (default 1): split-bf16 layer2 stride-1 convs on variant 31 (128-channel tiles)
-bool v31_identity_residual(int dtype, int cout, int Ho);  // bf16 layer3/4 identity blocks: the shortcut as variant 31's epilogue residual
-bool layer2_v31();  // SAD_L2_V31 (default 0; 1: measured 2.2-2.7 % slower): layer2's stride-1 convs on variant 31 (128-channel tiles)
-bool block_conv_can_pool(const BlockConvArgs& a, int dtype);  // default variant pools Ho x Wo tiles  // SAD_L2_HALO (default 1): layer2's identity blocks on the halo kernel
+// an identity BasicBlock's shortcut goes into conv2 as `res` (else as K columns over in1)
+bool identity_shortcut_is_res(int dtype, int x4, int cin, int cout, int stride, bool has_ds, int Ho);
+bool block_conv_can_pool(const BlockConvArgs& a, int dtype);  // default variant pools Ho x Wo tiles
 // dx (+)= col2im(dcol) (train.hip; the strided dgrad of wgrad.hip)
 int launch_col2im(const float* dcol, int64_t N, int H, int W, int C, int k, int stride, int pad, int Ho, int Wo,
                   int accumulate, void* dx, int dtype, hipStream_t s);
@@ -161,5 +159,38 @@ int fold_stem(const float* const* params, int dtype, void** w_out, float** b_out
 // only (a side above 512 would be point-sampled where the reference's
 // Resize((512,512)) applies its antialias filter).  SAD_ERR_ARG for such a map.
 int check_map_upsamples(int map_h, int map_w);
+
+// ---- one ResNet BasicBlock, folded for the block-conv kernels (basicblock.hip):
+// the ResNet-18 plan (api.hip) and the generic BasicBlock plans (resnet.hip)
+struct BasicBlock {
+  int cin = 0, cout = 0, stride = 1;
+  bool has_ds = false;
+  void* w1 = nullptr;   // conv1 + bn1: [cout][w1_ld = 9 * cin], plan dtype
+  float* b1 = nullptr;  // [cout]
+  int w1_ld = 0;
+  void* w2 = nullptr;   // conv2 + bn2, then the shortcut's K columns: [cout][w2_ld = 9 * cout + cin]
+  float* b2 = nullptr;  // (the identity matrix, or the folded 1x1/stride downsample; the shifts add)
+  int w2_ld = 0;
+};
+// One conv + BN group q (timm order: weight, BN weight / bias / mean / var) ->
+// [cout][k][k][cin] weights with BN's scale folded in float64, then the
+// shortcut's columns (ds: the downsample's group over ds_cin channels; identity:
+// a cout x cout identity) whose shift joins the bias; *ld = elements per row.
+int fold_conv(const float* const* q, int cout, int cin, int k, int dtype, void** w, float** b, int* ld,
+              const float* const* ds = nullptr, int ds_cin = 0, bool identity = false);
+// q1 = conv1 + bn1, q2 = conv2 + bn2, qd = downsample + bn or null (identity shortcut)
+int fold_basic_block(const float* const* q1, const float* const* q2, const float* const* qd, int cin, int cout,
+                     int stride, int dtype, BasicBlock& out);
+void free_basic_block(BasicBlock& b);
+// The block's launches on n images: x [n, H, H, cin] -> y [n, H/stride, H/stride, cout]
+// (NHWC, plan dtype; tmp holds conv1's output).  pool_out (optional): conv2 also
+// writes the global average pool when its kernel can; *pooled says whether it
+// did, and then y is not written.  bracket: the launches are recorded by the
+// sad_profile_* brackets (api.hip).
+int run_basic_block(const BasicBlock& b, int dtype, const void* x, void* tmp, void* y, int64_t n, int H, hipStream_t s,
+                    float* pool_out = nullptr, bool* pooled = nullptr, bool bracket = false);
+// launch_block_conv / launch_l1block inside a sad_profile_* bracket (api.hip)
+int timed_block_conv(const BlockConvArgs& a, int dtype, hipStream_t s, double flops);
+int timed_l1block(const L1BlockArgs& a, hipStream_t s, double flops);
 
 }  // namespace sad

@@ -6,12 +6,8 @@
 //
 // Launch plan per micro-batch (NHWC activations in the plan dtype):
 //   fused resize + stem (conv1 7x7/2 + bn1 + relu + maxpool)  -> X [128,128,64]
-//   BasicBlock:  T1 = relu(conv3x3/s(X))
-//                Y  = relu(conv3x3(T1) + shortcut)   the folded 1x1/s downsample
-//                     as extra K columns over X; the identity as an epilogue
-//                     residual where the halo / resident-weight kernels run
-//                     (else identity K columns); bf16 layer1 blocks as one
-//                     fused kernel (variant 40), as ResNet-18's plan
+//   BasicBlock:  run_basic_block (basicblock.hip), the block and the launches
+//                of ResNet-18's plan
 //   Bottleneck:  T1 = relu(conv1x1(X));  T2 = relu(conv3x3/s(T1))
 //                downsample block: Y = relu(conv1x1(T2) + ds(X)) as one GEMM
 //                (K = width + cin, shortcut pixels (oy*s, ox*s) of X)
@@ -23,9 +19,6 @@
 // Every conv is one launch of launch_block_conv (tile variant picked by
 // default_block_variant: the resident-weight / halo kernels for the 3x3/s1
 // convs that qualify); BN is folded into weights and bias.
-#include <math.h>
-#include <stdlib.h>
-
 #include <algorithm>
 #include <vector>
 
@@ -43,50 +36,22 @@ struct ConvW {
   int ld = 0;         // elements per weight row
 };
 
-struct Block {
+struct Bottleneck {
   int cin, width, cout, stride;
   bool has_ds;
-  ConvW c1, c2, c3;  // Basic: c1, c2 (+ shortcut columns); Bottleneck: c1, c2, c3 (+ ds columns)
+  ConvW c1, c2, c3;  // c3 + the downsample's K columns
 };
 
 int fold_conv(const float* const* q, int cout, int cin, int k, int dtype, ConvW& out,
-              const float* const* ds = nullptr, int ds_cin = 0, bool identity = false) {
-  std::vector<double> sc, sh, scd, shd;
-  fold_bn(q[1], q[2], q[3], q[4], cout, sc, sh);
-  if (ds) fold_bn(ds[1], ds[2], ds[3], ds[4], cout, scd, shd);
-  const int kk = k * k * cin;
-  const int extra = ds ? ds_cin : (identity ? cout : 0);
-  const int ld = kk + extra;
-  std::vector<double> w((size_t)cout * ld, 0.0);
-  std::vector<float> b(cout);
-  const float* W = q[0];
-  for (int o = 0; o < cout; ++o) {
-    for (int c = 0; c < cin; ++c)
-      for (int t = 0; t < k * k; ++t)  // timm [Cout][Cin][KH][KW] -> [Cout][KH][KW][Cin]
-        w[(size_t)o * ld + (size_t)t * cin + c] = (double)W[((size_t)o * cin + c) * k * k + t] * sc[o];
-    double bias = sh[o];
-    if (ds) {
-      for (int c = 0; c < ds_cin; ++c) w[(size_t)o * ld + kk + c] = (double)ds[0][(size_t)o * ds_cin + c] * scd[o];
-      bias += shd[o];
-    } else if (identity) {
-      w[(size_t)o * ld + kk + o] = 1.0;  // exact in bf16
-    }
-    b[o] = (float)bias;
-  }
+              const float* const* ds = nullptr, int ds_cin = 0) {
   out.cin = cin;
   out.cout = cout;
   out.k = k;
-  out.ld = ld;
-  int rc;
-  if ((rc = upload_typed(&out.w, w, dtype, ld))) return rc;
-  return upload((void**)&out.b, b);
+  return sad::fold_conv(q, cout, cin, k, dtype, &out.w, &out.b, &out.ld, ds, ds_cin);
 }
 
 bool deep_x4() {
-  static const bool on = [] {
-    const char* e = getenv("SAD_DEEP_X4");
-    return !(e && atoi(e) == 0);
-  }();
+  static const bool on = env_int("SAD_DEEP_X4", 1) != 0;
   return on;
 }
 
@@ -109,7 +74,8 @@ struct sad_resnet_plan {
   void* stem_w = nullptr;
   float* stem_b = nullptr;
   float* stem_w3 = nullptr;  // distinct-channel stem (sad_resnet_run_img3)
-  std::vector<Block> blocks;
+  std::vector<BasicBlock> basic;   // SAD_BASIC_BLOCK plans
+  std::vector<Bottleneck> blocks;  // SAD_BOTTLENECK plans
   int64_t max_elems = 0;  // largest activation per segment (elements)
 };
 
@@ -118,6 +84,7 @@ extern "C" int sad_resnet_plan_destroy(sad_resnet_plan* p) {
   (void)hipFree(p->stem_w);
   (void)hipFree(p->stem_b);
   (void)hipFree(p->stem_w3);
+  for (auto& b : p->basic) free_basic_block(b);
   for (auto& b : p->blocks) {
     free_conv(b.c1);
     free_conv(b.c2);
@@ -166,38 +133,30 @@ extern "C" int sad_resnet_plan_create(const float* const* params, int32_t n_para
   p->max_elems = (int64_t)H * H * 64;
   for (int li = 0; li < 4; ++li) {
     for (int b = 0; b < layers[li]; ++b) {
-      Block blk{};
-      blk.stride = (b == 0 && li > 0) ? 2 : 1;
-      blk.cin = inp;
-      blk.width = planes[li];
-      blk.cout = planes[li] * exp;
-      blk.has_ds = b == 0 && (blk.stride != 1 || inp != blk.cout);
+      const int stride = (b == 0 && li > 0) ? 2 : 1, cout = planes[li] * exp;
+      const bool has_ds = b == 0 && (stride != 1 || inp != cout);
       const float* const* q1 = params + 5 * gi++;
       const float* const* q2 = params + 5 * gi++;
       const float* const* q3 = block == SAD_BOTTLENECK ? params + 5 * gi++ : nullptr;
-      const float* const* qd = blk.has_ds ? params + 5 * gi++ : nullptr;
-      const int Ho = H / blk.stride;
+      const float* const* qd = has_ds ? params + 5 * gi++ : nullptr;
+      const int Ho = H / stride;
       if (block == SAD_BASIC_BLOCK) {
-        if ((rc = fold_conv(q1, blk.cout, inp, 3, dtype, blk.c1)) ||
-            (rc = fold_conv(q2, blk.cout, blk.cout, 3, dtype, blk.c2, qd, inp, !blk.has_ds))) {
-          p->blocks.push_back(blk);
-          sad_resnet_plan_destroy(p);
-          return rc;
-        }
-        p->max_elems = std::max<int64_t>(p->max_elems, (int64_t)Ho * Ho * blk.cout);
+        p->basic.emplace_back();
+        rc = fold_basic_block(q1, q2, qd, inp, cout, stride, dtype, p->basic.back());
       } else {
-        if ((rc = fold_conv(q1, blk.width, inp, 1, dtype, blk.c1)) ||
-            (rc = fold_conv(q2, blk.width, blk.width, 3, dtype, blk.c2)) ||
-            (rc = fold_conv(q3, blk.cout, blk.width, 1, dtype, blk.c3, qd, inp, false))) {
-          p->blocks.push_back(blk);
-          sad_resnet_plan_destroy(p);
-          return rc;
-        }
+        p->blocks.push_back(Bottleneck{inp, planes[li], cout, stride, has_ds, {}, {}, {}});
+        Bottleneck& blk = p->blocks.back();
+        rc = fold_conv(q1, blk.width, inp, 1, dtype, blk.c1);
+        if (!rc) rc = fold_conv(q2, blk.width, blk.width, 3, dtype, blk.c2);
+        if (!rc) rc = fold_conv(q3, cout, blk.width, 1, dtype, blk.c3, qd, inp);
         p->max_elems = std::max<int64_t>(p->max_elems, (int64_t)H * H * blk.width);
-        p->max_elems = std::max<int64_t>(p->max_elems, (int64_t)Ho * Ho * blk.cout);
       }
-      p->blocks.push_back(blk);
-      inp = blk.cout;
+      if (rc) {
+        sad_resnet_plan_destroy(p);
+        return rc;
+      }
+      p->max_elems = std::max<int64_t>(p->max_elems, (int64_t)Ho * Ho * cout);
+      inp = cout;
       H = Ho;
     }
   }
@@ -259,20 +218,6 @@ static int rn_block_conv(const sad_resnet_plan* p, const ConvW& c, const void* x
   return launch_block_conv(a, p->dtype, s);
 }
 
-// BasicBlock conv2 whose identity shortcut goes in as an epilogue residual
-// (ResNet-18's plan, api.hip run_blocks): stride 1, no downsample, 16 x 16
-// tiles, Cout <= 64, or Cout <= 128 where layer2 runs the halo / resident-weight
-// kernels, or (bf16) Cout a multiple of 256 where layer3/4 run variant 31,
-// which adds it in fp32 to the accumulators (the split-bf16 mode's variants
-// 30 / 31 take the identity as K columns)
-static bool identity_epilogue(const sad_resnet_plan* p, const Block& b, int Ho) {
-  const int dtype = p->dtype;
-  if (p->x4 || !(dtype == SAD_BF16 || dtype == SAD_BF16X3) || b.stride != 1 || b.has_ds || Ho % 16 != 0) return false;
-  return b.cout <= 64 || (b.cout <= 128 && layer2_halo() && !(dtype == SAD_BF16 && layer2_v31()) &&
-                          !(dtype == SAD_BF16X3 && x3_layer2_v31())) ||
-         v31_identity_residual(dtype, b.cout, Ho);
-}
-
 static int rn_chunk(const sad_resnet_plan* p, const float* map, const float* img, int64_t n, float* feats, char* ws,
                     hipStream_t s, const float* img3 = nullptr) {
   const size_t ab = rn_act_bytes(p, n);
@@ -285,43 +230,20 @@ static int rn_chunk(const sad_resnet_plan* p, const float* map, const float* img
   st.x4 = p->x4;
   if ((rc = launch_stem(st, p->dtype, s))) return rc;
   int H = 128, C = 64;
-  for (const Block& b : p->blocks) {
+  for (const BasicBlock& b : p->basic) {
+    if ((rc = run_basic_block(b, p->dtype, X, T1, Y, n, H, s))) return rc;
+    std::swap(X, Y);
+    H /= b.stride;
+    C = b.cout;
+  }
+  for (const Bottleneck& b : p->blocks) {
     const int Ho = H / b.stride;
-    if (p->block == SAD_BASIC_BLOCK) {
-      if (p->dtype == SAD_BF16 && b.stride == 1 && !b.has_ds && b.cin == 64 && b.cout == 64 && H % 16 == 0 &&
-          l1_fused()) {
-        // layer1: the whole BasicBlock as one kernel (variant 40), as ResNet-18's plan
-        L1BlockArgs f{};
-        f.x = (const u16*)X;
-        f.out = (u16*)Y;
-        f.N = (int)n;
-        f.H = f.W = H;
-        f.w1 = (const u16*)b.c1.w;
-        f.w1_ld = b.c1.ld;
-        f.b1 = b.c1.b;
-        f.w2 = (const u16*)b.c2.w;
-        f.w2_ld = b.c2.ld;  // 576 + the identity's 64 K columns (not read: the residual is the patch centre)
-        f.b2 = b.c2.b;
-        if ((rc = launch_l1block(f, s))) return rc;
-      } else {
-        if ((rc = rn_block_conv(p, b.c1, X, n, H, b.stride, nullptr, 0, 0, 1, T1, s))) return rc;
-        if (identity_epilogue(p, b, Ho)) {
-          // identity blocks of layer1/2 (and bf16 layer3/4): the shortcut as an
-          // epilogue add on the halo / resident-weight kernels / variant 31 (as
-          // ResNet-18's plan), not as identity K columns
-          if ((rc = rn_block_conv(p, b.c2, T1, n, Ho, 1, nullptr, 0, 0, 1, Y, s, X))) return rc;
-        } else {
-          if ((rc = rn_block_conv(p, b.c2, T1, n, Ho, 1, X, H, C, b.stride, Y, s))) return rc;
-        }
-      }
+    if ((rc = rn_block_conv(p, b.c1, X, n, H, 1, nullptr, 0, 0, 1, T1, s))) return rc;
+    if ((rc = rn_block_conv(p, b.c2, T1, n, H, b.stride, nullptr, 0, 0, 1, T2, s))) return rc;
+    if (b.has_ds) {
+      if ((rc = rn_block_conv(p, b.c3, T2, n, Ho, 1, X, H, C, b.stride, Y, s))) return rc;
     } else {
-      if ((rc = rn_block_conv(p, b.c1, X, n, H, 1, nullptr, 0, 0, 1, T1, s))) return rc;
-      if ((rc = rn_block_conv(p, b.c2, T1, n, H, b.stride, nullptr, 0, 0, 1, T2, s))) return rc;
-      if (b.has_ds) {
-        if ((rc = rn_block_conv(p, b.c3, T2, n, Ho, 1, X, H, C, b.stride, Y, s))) return rc;
-      } else {
-        if ((rc = rn_block_conv(p, b.c3, T2, n, Ho, 1, nullptr, 0, 0, 1, Y, s, X))) return rc;
-      }
+      if ((rc = rn_block_conv(p, b.c3, T2, n, Ho, 1, nullptr, 0, 0, 1, Y, s, X))) return rc;
     }
     std::swap(X, Y);
     H = Ho;

@@ -850,10 +850,7 @@ extern "C" int sad_conv_bn_train_workspace_size(int64_t N, int32_t H, int32_t W,
 // resident-weight variants with fused statistics (round 4): 128 -> 128 on
 // variant 41, the stride-2 64 -> 128 on variant 43; 0 = variants 20 / 15
 static bool train_l2_rw() {
-  static const bool v = [] {
-    const char* e = getenv("SAD_TRAIN_L2_RW");
-    return e ? atoi(e) != 0 : true;
-  }();
+  static const bool v = env_int("SAD_TRAIN_L2_RW", 1) != 0;
   return v;
 }
 

@@ -9,9 +9,8 @@ ReLU) under a-priori bars:
   ReLU   where the float64 pre-activation is <= -(accumulation bar) the
          output must be exactly 0
 
-The heads' two wide layers, sad_conv2d_run and SAD_BACKBONE_PATH=igemm stand
-on this kernel.  Shapes are the smallest that reach each edge: 1, 2 and 3
-K-steps (the three-stage variants' ring start-up), M below one tile, M one
+The heads' two wide layers and sad_conv2d_run stand on this kernel.  Shapes
+are the smallest that reach each edge: 1, 2 and 3 K-steps (the three-stage variants' ring start-up), M below one tile, M one
 past a multiple of every BM (128, 256, 512), H != W with odd sizes at 3x3
 stride 1 and 2, 1x1 stride 2, 7x7 stride 2 pad 3, with and without residual
 and ReLU, N = 0.  The image's border pixels carry large values, so that a

@@ -1,7 +1,10 @@
 """A/B helper (GPU box): the front end's dB + standardised maps, the stem and
 the merged logits of one library build (SAD_LIB) on a fixed synthetic batch,
 saved to an .npz as SHA-256 digests plus the first 2 segments (the files stay
-small) -- two builds' files are then compared bit for bit.
+small) -- two builds' files are then compared bit for bit.  Also digested: an
+fp32 engine's merged logits on 32 segments, a resnet34 ResNetBackbone's pooled
+features in the three dtypes on 8 segments, and Backbone.shared's per-tail
+features for two tails on 8 segments.  The digests are printed, one per line.
     SAD_LIB=tools/_libsad_base.so python tools/lib_bits.py out_base.npz"""
 import os
 import sys
@@ -31,11 +34,28 @@ def main():
         out[f'{dt}_maps'] = maps.cpu().numpy()
         out[f'{dt}_stem'] = eng.backbones[0].stem(maps[:64]).float().cpu().numpy()
         out[f'{dt}_merged'] = merged.cpu().numpy()
+    from sad import weights as sw
+    from sad.engine import Backbone, ResNetBackbone, split_merged_state
+    eng = Engine(merged_sd('n6'), dev, dtype='fp32', micro_batch=16)
+    out['fp32_merged'] = eng.forward_pcm(pcm[:32])[1].cpu().numpy()
+    maps8 = maps[:8].contiguous()
+    gold = os.path.join(ROOT, 'tests', 'golden')
+    r34 = split_merged_state(sw.merged_state_dict(
+        0, 1, bn_stats=sw.load_bn_stats(os.path.join(gold, 'bn_stats_resnet34.npz')), model_name='resnet34'))[1][0]
+    bases = split_merged_state(merged_sd('n2'))[1]  # two distinct backbones: the second as a tail of the first
+    for dt in ('fp32', 'bf16', 'bf16x3'):
+        out[f'{dt}_resnet34_feats'] = ResNetBackbone(r34, 'resnet34', dev, dt, micro_batch=4)(maps8).cpu().numpy()
+        bbs = [Backbone(b, dev, dt, micro_batch=4) for b in (bases[0], bases[1])]
+        for t, f in enumerate(bbs[0].shared(bbs, maps8)):
+            out[f'{dt}_shared_tail{t}'] = f.cpu().numpy()
     small = {}
     for k, v in out.items():
         small[k + '_sha256'] = np.frombuffer(hashlib.sha256(np.ascontiguousarray(v).tobytes()).digest(), np.uint8)
         if not k.endswith('_stem'):
             small[k + '_head'] = v[:2]
+    for k in sorted(small):
+        if k.endswith('_sha256'):
+            print(k[:-7], small[k].tobytes().hex())
     np.savez(sys.argv[1], **small)
 
 
