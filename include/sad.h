@@ -55,10 +55,21 @@ enum sad_status {
 enum sad_dtype {
   SAD_F32 = 0,   /* fp32 activations, f32 MFMA (v_mfma_f32_16x16x4_f32): parity mode */
   SAD_BF16 = 1,  /* bf16 activations, bf16 MFMA (v_mfma_f32_16x16x32_bf16), f32 accumulate */
-  SAD_BF16X3 = 2 /* split-bf16 parity mode: every value v stored as hi = bf16(v), lo = bf16(v - hi)
+  SAD_BF16X3 = 2, /* split-bf16 parity mode: every value v stored as hi = bf16(v), lo = bf16(v - hi)
                     (channels interleaved [hi 32 | lo 32] per group of 32, 4 B per value like fp32);
                     each product = W_hi.X_hi + W_lo.X_hi + W_hi.X_lo on bf16 MFMA, f32 accumulate:
                     ~2^-17 relative operands, 3x the bf16 MFMA work, 16/3 x the f32 MFMA rate */
+  SAD_F16 = 3    /* IEEE binary16 activations and weights, f16 MFMA (v_mfma_f32_16x16x32_f16), f32
+                    accumulate: SAD_BF16's layouts (NHWC, the same weight packs, 2 B per value), kernels,
+                    variants and grids with 11 significant bits instead of 8.  Inference only: the
+                    backbone / ResNet plans and their runs, sad_conv2d_run, sad_block_conv_run,
+                    sad_l1_block_run, sad_pack_conv_weight_run, sad_avgpool_run.
+                    RANGE: a plan whose folded weights exceed 65,504 in magnitude, or whose folded
+                    weights or biases are not finite, is refused (SAD_ERR_ARG, the message names the
+                    conv).  Every fp16 activation store SATURATES a finite value to +-65,504 instead of
+                    writing inf, and it does so SILENTLY: no error, no flag.  PRECONDITION: finite
+                    inputs (maps, images, activations, biases).  The saturation is the hardware's
+                    fp16-overflow clamp, which keeps a value that already is inf or NaN in fp32. */
 };
 
 /* ---------------------------------------------------------------- runtime */
@@ -353,6 +364,7 @@ int sad_backbone_run_debug(const sad_backbone_plan* plan, const float* map, int6
  *
  * l3: layer3's output, NHWC [B, 32, 32, 256] in the plan's activation layout:
  *   SAD_BF16    bf16, 256 values per pixel (512 B)
+ *   SAD_F16     fp16 (IEEE binary16), 256 values per pixel (512 B)
  *   SAD_F32     fp32, 256 values per pixel (1 KiB)
  *   SAD_BF16X3  split-bf16, 512 bf16 per pixel (1 KiB): per group of 32
  *               channels [hi(32) | lo(32)], hi = bf16(x), lo = bf16(x - hi)
@@ -520,9 +532,11 @@ int sad_block_conv_run(const void* in0, int64_t N, int32_t H, int32_t W, int32_t
  * intermediate stays in LDS and the identity comes from the input patch.
  * Replaces the two sad_block_conv_run launches (conv1; conv2 + res) of a
  * layer1 block -- reference inference_runner.py:49-51 (timm forward_features).
- * bf16 only.  x, out: NHWC [N,H,W,64] bf16 (must not overlap), H and W
- * multiples of 16; w1, w2: [64][w_ld] bf16, k = tap * 64 + ci; b1, b2: [64]
- * fp32.  ablate: reserved, pass 0.  Async on `stream`. */
+ * bf16, or fp16 with SAD_L1_BLOCK_F16.  x, out: NHWC [N,H,W,64] bf16 (must
+ * not overlap), H and W multiples of 16; w1, w2: [64][w_ld] bf16, k = tap * 64
+ * + ci; b1, b2: [64] fp32.  ablate: reserved, pass 0, or SAD_L1_BLOCK_F16:
+ * every tensor is fp16 (SAD_F16) instead of bf16.  Async on `stream`. */
+#define SAD_L1_BLOCK_F16 0x10000
 int sad_l1_block_run(const void* x, int64_t N, int32_t H, int32_t W, const void* w1, int32_t w1_ld,
                      const float* b1, const void* w2, int32_t w2_ld, const float* b2, void* out,
                      int32_t ablate, void* stream);

@@ -40,7 +40,7 @@ from sad import launch as _launch  # noqa: E402
 from sad import scan as _scan  # noqa: E402
 from sad import weights as _weights  # noqa: E402
 
-DEFAULT_BATCH = {'bf16': 2048, 'bf16x3': 512, 'fp32': 128}  # as bench.py
+DEFAULT_BATCH = {'bf16': 2048, 'fp16': 2048, 'bf16x3': 512, 'fp32': 128}  # as bench.py (fp16: bf16's)
 
 
 def list_files(args) -> list:
@@ -59,10 +59,10 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument('--output-json', type=str, default='results.json', help='one JSON list, a record per file')
     p.add_argument('--threshold', type=float, default=0.5, help='Threshold for deciding Real vs Synthetic')
     p.add_argument('--smooth', action='store_true', help='Apply smoothing across a file\'s windows.')
-    p.add_argument('--precision', choices=['fp32', 'bf16x3', 'bf16'], default='fp32')
+    p.add_argument('--precision', choices=['fp32', 'bf16x3', 'bf16', 'fp16'], default='fp32')
     p.add_argument('--model-name', default='resnet18', choices=list(_weights.ARCHS))
     p.add_argument('--batch-size', type=int, default=0,
-                   help='windows per device batch (0: 2048 bf16, 512 bf16x3, 128 fp32)')
+                   help='windows per device batch (0: 2048 bf16 / fp16, 512 bf16x3, 128 fp32)')
     p.add_argument('--pack-seconds', type=float, default=_scan.DEFAULT_PACK_SECONDS,
                    help='seconds of 32 kHz audio per pack (one upload and one host wait each)')
     p.add_argument('--workers', type=int, default=_scan.DEFAULT_WORKERS,

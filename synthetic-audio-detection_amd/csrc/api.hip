@@ -95,9 +95,30 @@ int upload_typed(void** dst, const std::vector<double>& v, int dtype, int64_t ro
     for (size_t i = 0; i < v.size(); ++i) h[i] = f2bf_host((float)v[i]);
     return upload(dst, h);
   }
+  if (dtype == SAD_F16) {  // (the folds check the range first: check_f16_range)
+    std::vector<u16> h(v.size());
+    for (size_t i = 0; i < v.size(); ++i) h[i] = f2h_host((float)v[i]);
+    return upload(dst, h);
+  }
   std::vector<float> h(v.size());
   for (size_t i = 0; i < v.size(); ++i) h[i] = (float)v[i];
   return upload(dst, h);
+}
+
+int check_f16_range(const std::vector<double>& w, const std::vector<float>& b, const std::string& name) {
+  for (size_t i = 0; i < w.size(); ++i)
+    if (!(fabs(w[i]) <= (double)F16_MAX)) {  // (also NaN)
+      set_error("argument check failed: fp16 plan: folded weight " + std::to_string(i) + " of " + name + " is " +
+                std::to_string(w[i]) + ": not finite or beyond fp16's largest value 65504");
+      return SAD_ERR_ARG;
+    }
+  for (size_t i = 0; i < b.size(); ++i)
+    if (!std::isfinite(b[i])) {
+      set_error("argument check failed: fp16 plan: folded bias " + std::to_string(i) + " of " + name +
+                " is not finite");
+      return SAD_ERR_ARG;
+    }
+  return SAD_OK;
 }
 
 // conv1 7x7/2 + bn1 folded for the stem kernel, the 3 identical input channels
@@ -107,7 +128,7 @@ int fold_stem(const float* const* params, int dtype, void** w_out, float** b_out
   std::vector<double> sc, sh;
   fold_bn(params[1], params[2], params[3], params[4], 64, sc, sh);
   std::vector<double> w(64 * 64, 0.0);
-  const int wdt = dtype == SAD_BF16X3 ? SAD_BF16 : dtype;  // split stem: bf16 layout, hi then lo
+  const int wdt = dtype == SAD_BF16X3 || dtype == SAD_F16 ? SAD_BF16 : dtype;  // split stem: bf16 layout, hi then lo; fp16: bf16's
   std::vector<float> b(64);
   for (int co = 0; co < 64; ++co) {
     for (int k = 0; k < 49; ++k) {
@@ -120,6 +141,7 @@ int fold_stem(const float* const* params, int dtype, void** w_out, float** b_out
     b[co] = (float)sh[co];
   }
   int rc;
+  if (dtype == SAD_F16 && (rc = check_f16_range(w, b, "conv1"))) return rc;
   {  // [64 co][3 c][49 k] fp32, BN scale folded (distinct-channel stem)
     std::vector<float> w3(64 * 3 * 49);
     for (int co = 0; co < 64; ++co)
@@ -157,7 +179,7 @@ extern "C" int sad_backbone_plan_create(const float* const* params, int32_t n_pa
                                         int32_t map_h, int32_t map_w, sad_backbone_plan** out) {
   SAD_REQUIRE(params && out, "null params/out");
   SAD_REQUIRE(n_params == 20 * 5, "n_params must be 100 (20 conv+BN groups)");
-  SAD_REQUIRE(dtype == SAD_F32 || dtype == SAD_BF16 || dtype == SAD_BF16X3, "dtype");
+  SAD_REQUIRE(dtype == SAD_F32 || dtype == SAD_BF16 || dtype == SAD_BF16X3 || dtype == SAD_F16, "dtype");
   SAD_REQUIRE(map_h > 0 && map_w > 0, "map shape");
   if (int rc = check_map_upsamples(map_h, map_w)) return rc;
   for (int i = 0; i < n_params; ++i) SAD_REQUIRE(params[i] != nullptr, "null parameter pointer");
@@ -184,8 +206,9 @@ extern "C" int sad_backbone_plan_create(const float* const* params, int32_t n_pa
     for (int b = 0; b < 2; ++b) {
       const bool has_ds = b == 0 && li > 0;
       p->blocks.emplace_back();
+      const std::string name = "layer" + std::to_string(li + 1) + "." + std::to_string(b);
       if ((rc = fold_basic_block(q, q + 5, has_ds ? q + 10 : nullptr, inp, 64 << li, has_ds ? 2 : 1, dtype,
-                                 p->blocks.back()))) {
+                                 p->blocks.back(), name.c_str()))) {
         sad_backbone_plan_destroy(p);
         return rc;
       }
@@ -209,7 +232,7 @@ extern "C" int sad_backbone_plan_destroy(sad_backbone_plan* p) {
 
 static constexpr int64_t kMaxActElems = 128ll * 128 * 64;  // per segment, layer1 map
 static size_t act_bytes(const sad_backbone_plan* p, int64_t mb) {
-  const size_t es = p->dtype == SAD_BF16 ? 2 : 4;  // fp32 and split-bf16: 4 B per value
+  const size_t es = dtype_bytes(p->dtype);  // fp32 and split-bf16: 4 B per value
   return ((size_t)mb * kMaxActElems * es + 255) & ~(size_t)255;
 }
 
@@ -234,7 +257,7 @@ static std::vector<ProfRec> g_prof;
 
 int sad::timed_block_conv(const BlockConvArgs& a, int dtype, hipStream_t s, double flops) {
   if (!g_prof_on) return launch_block_conv(a, dtype, s);
-  ProfRec r{default_block_variant(a, dtype), flops, nullptr, nullptr, 0};
+  ProfRec r{a.x4 ? gemm_block_variant(a) : default_block_variant(a, dtype), flops, nullptr, nullptr, 0};
   SAD_CHECK_HIP(hipEventCreate(&r.e0));
   SAD_CHECK_HIP(hipEventCreate(&r.e1));
   SAD_CHECK_HIP(hipEventRecord(r.e0, s));
@@ -358,7 +381,7 @@ static int front_sub_batch(int dtype) {
   // split-bf16 (layer1 on variant 42): 64, +0.8 % over 32 in the parity mode
   // (same box, 2 rounds; 128 and the whole micro-batch are slower,
   // profiles/r04_x3_frontmb_ab.log)
-  return dtype == SAD_BF16 && l1_fused() ? 256 : dtype == SAD_BF16X3 ? 64 : 32;
+  return is16(dtype) && l1_fused() ? 256 : dtype == SAD_BF16X3 ? 64 : 32;
 }
 
 // Stem + layer1 of the block path on mb segments, per sub-chunk of
@@ -366,7 +389,7 @@ static int front_sub_batch(int dtype) {
 static int run_front(const sad_backbone_plan* p, const float* map, const float* img, const float* img3, int64_t mb,
                      void* bufA, void* bufB, void* bufT, void* bufD, int& H, int& C, hipStream_t s) {
   int rc;
-  const size_t es = p->dtype == SAD_BF16 ? 2 : 4;
+  const size_t es = dtype_bytes(p->dtype);
   const int64_t f = front_sub_batch(p->dtype) > 0 ? std::min<int64_t>(front_sub_batch(p->dtype), mb) : mb;
   // stem + layer1 per sub-chunk of f segments (Infinity-Cache-sized); layer1's
   // output ([f, 128, 128, 64] per sub-chunk) is gathered in bufD, then layers
@@ -413,7 +436,7 @@ static int run_chunk(const sad_backbone_plan* p, const float* map, const float* 
     return rc;
   bufA = a0;
   if (layer4_out) {
-    const size_t es = p->dtype == SAD_BF16 ? 2 : 4;
+    const size_t es = dtype_bytes(p->dtype);
     SAD_CHECK_HIP(hipMemcpyAsync(layer4_out, bufA, (size_t)mb * H * H * C * es, hipMemcpyDeviceToDevice, s));
   }
   if (pooled) return SAD_OK;
@@ -426,7 +449,7 @@ static int run_chunk(const sad_backbone_plan* p, const float* map, const float* 
 // trunk + tail is bit-identical to sad_backbone_run*.
 static constexpr int64_t kL3Elems = 32ll * 32 * 256;  // per segment, layer3 output
 static size_t l3_bytes(const sad_backbone_plan* p, int64_t n) {
-  return (size_t)n * kL3Elems * (p->dtype == SAD_BF16 ? 2 : 4);
+  return (size_t)n * kL3Elems * (dtype_bytes(p->dtype));
 }
 
 // stem .. layer3 on mb segments -> l3_out [mb, 32, 32, 256] (plan layout)
@@ -857,7 +880,7 @@ extern "C" int sad_conv2d_run(const void* in, int64_t N, int32_t H, int32_t W, i
                               void* stream) {
   SAD_REQUIRE(in && wt && bias && out, "null tensor");
   SAD_REQUIRE(N >= 0 && H > 0 && W > 0 && k > 0 && stride > 0 && pad >= 0, "bad shape");
-  SAD_REQUIRE(dtype == SAD_F32 || dtype == SAD_BF16, "dtype");
+  SAD_REQUIRE(dtype == SAD_F32 || dtype == SAD_BF16 || dtype == SAD_F16, "dtype");
   ConvArgs a{};
   a.in = in;
   a.in_pstride = Cin;
@@ -902,7 +925,8 @@ extern "C" int sad_l1_block_run(const void* x, int64_t N, int32_t H, int32_t W, 
   a.w2 = (const u16*)w2;
   a.w2_ld = w2_ld;
   a.b2 = b2;
-  a.ablate = ablate;
+  a.ablate = ablate & 0xFFFF;
+  a.h16 = (ablate & SAD_L1_BLOCK_F16) != 0;
   return launch_l1block(a, (hipStream_t)stream);
 }
 
@@ -913,7 +937,7 @@ extern "C" int sad_block_conv_run(const void* in0, int64_t N, int32_t H, int32_t
                                   int32_t variant, void* stream) {
   SAD_REQUIRE(in0 && wt && bias && out, "null tensor");
   SAD_REQUIRE(N >= 0 && H > 0 && W > 0 && k > 0 && stride > 0 && pad >= 0, "bad shape");
-  SAD_REQUIRE(dtype == SAD_F32 || dtype == SAD_BF16 || dtype == SAD_BF16X3, "dtype");
+  SAD_REQUIRE(dtype == SAD_F32 || dtype == SAD_BF16 || dtype == SAD_BF16X3 || dtype == SAD_F16, "dtype");
   BlockConvArgs a{};
   a.in0 = in0;
   a.in0_pstride = Cin;

@@ -5,7 +5,7 @@
 //   Y = relu(conv3x3(T) + shortcut)   the folded 1x1/s downsample as extra K
 //       columns over X; the identity as an epilogue residual or as identity K
 //       columns (identity_shortcut_is_res, block.hip)
-//   bf16 layer1 blocks (64 -> 64) as one fused kernel (variant 40, l1block.hip)
+//   bf16 / fp16 layer1 blocks (64 -> 64) as one fused kernel (variant 40, l1block.hip)
 #include <vector>
 
 #include "common.hpp"
@@ -14,7 +14,7 @@
 namespace sad {
 
 int fold_conv(const float* const* q, int cout, int cin, int k, int dtype, void** w_out, float** b_out, int* ld_out,
-              const float* const* ds, int ds_cin, bool identity) {
+              const float* const* ds, int ds_cin, bool identity, const char* name) {
   std::vector<double> sc, sh, scd, shd;
   fold_bn(q[1], q[2], q[3], q[4], cout, sc, sh);
   if (ds) fold_bn(ds[1], ds[2], ds[3], ds[4], cout, scd, shd);
@@ -39,19 +39,21 @@ int fold_conv(const float* const* q, int cout, int cin, int k, int dtype, void**
   }
   *ld_out = ld;
   int rc;
+  if (dtype == SAD_F16 && (rc = check_f16_range(w, b, name))) return rc;
   if ((rc = upload_typed(w_out, w, dtype, ld))) return rc;
   return upload((void**)b_out, b);
 }
 
 int fold_basic_block(const float* const* q1, const float* const* q2, const float* const* qd, int cin, int cout,
-                     int stride, int dtype, BasicBlock& out) {
+                     int stride, int dtype, BasicBlock& out, const char* name) {
   out.cin = cin;
   out.cout = cout;
   out.stride = stride;
   out.has_ds = qd != nullptr;
   int rc;
-  if ((rc = fold_conv(q1, cout, cin, 3, dtype, &out.w1, &out.b1, &out.w1_ld))) return rc;
-  return fold_conv(q2, cout, cout, 3, dtype, &out.w2, &out.b2, &out.w2_ld, qd, cin, !qd);
+  const std::string n1 = std::string(name) + ".conv1", n2 = std::string(name) + (qd ? ".conv2 + downsample" : ".conv2");
+  if ((rc = fold_conv(q1, cout, cin, 3, dtype, &out.w1, &out.b1, &out.w1_ld, nullptr, 0, false, n1.c_str()))) return rc;
+  return fold_conv(q2, cout, cout, 3, dtype, &out.w2, &out.b2, &out.w2_ld, qd, cin, !qd, n2.c_str());
 }
 
 void free_basic_block(BasicBlock& b) {
@@ -66,7 +68,7 @@ void free_basic_block(BasicBlock& b) {
 int run_basic_block(const BasicBlock& blk, int dtype, const void* x, void* tmp, void* y, int64_t n, int H,
                     hipStream_t s, float* pool_out, bool* pooled, bool bracket) {
   const int C = blk.cin, Ho = H / blk.stride;
-  if (dtype == SAD_BF16 && blk.stride == 1 && !blk.has_ds && C == 64 && blk.cout == 64 && H % 16 == 0 && l1_fused()) {
+  if (is16(dtype) && blk.stride == 1 && !blk.has_ds && C == 64 && blk.cout == 64 && H % 16 == 0 && l1_fused()) {
     // layer1: the whole BasicBlock as one kernel (variant 40)
     L1BlockArgs f{};
     f.x = (const u16*)x;
@@ -79,6 +81,7 @@ int run_basic_block(const BasicBlock& blk, int dtype, const void* x, void* tmp, 
     f.w2 = (const u16*)blk.w2;
     f.w2_ld = blk.w2_ld;  // 576 + the identity's 64 K columns (not read: the residual is the patch centre)
     f.b2 = blk.b2;
+    f.h16 = dtype == SAD_F16;
     return bracket ? timed_l1block(f, s, 2.0 * 2.0 * n * H * H * 64 * 576.0) : launch_l1block(f, s);
   }
   int rc;

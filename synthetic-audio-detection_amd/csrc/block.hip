@@ -110,6 +110,7 @@ __global__ __launch_bounds__(64 * WC * WP, OCC * WC * WP / 4) void block_conv_ke
   static_assert(S == 2 || S == 3, "ring depth");
   static_assert(!X3 || sizeof(T) == 2, "split-bf16 operands are bf16");
   static_assert(!X4 || (X3 && !ST), "X4 is the split-bf16 inference form's fourth product");
+  f16_kernel_entry<T>();
   constexpr int NW = WC * WP;
   constexpr int BC = 16 * TC * WC, BP = 16 * TP * WP;  // channels x pixels per tile
   constexpr int ES = sizeof(T);
@@ -566,6 +567,11 @@ if constexpr (X3) {
                   v[1] += bf2f((u16)(q.x >> 16)) + bf2f((u16)(l.x >> 16));
                   v[2] += bf2f((u16)(q.y & 0xFFFF)) + bf2f((u16)(l.y & 0xFFFF));
                   v[3] += bf2f((u16)(q.y >> 16)) + bf2f((u16)(l.y >> 16));
+                } else if constexpr (is_f16_v<T>) {
+                  v[0] += lo16<f16>(q.x);
+                  v[1] += hi16<f16>(q.x);
+                  v[2] += lo16<f16>(q.y);
+                  v[3] += hi16<f16>(q.y);
                 } else {
                   v[0] += bf2f((u16)(q.x & 0xFFFF));
                   v[1] += bf2f((u16)(q.x >> 16));
@@ -597,7 +603,9 @@ if constexpr (X3) {
               continue;
             }
             T* op = out + (int64_t)px * a.out_pstride + co;
-            if constexpr (sizeof(T) == 2) {
+            if constexpr (is_f16_v<T>) {  // (saturating)
+              *(uint2*)op = make_uint2(pk_f16(v[0], v[1]), pk_f16(v[2], v[3]));
+            } else if constexpr (sizeof(T) == 2) {
               uint2 q;
               q.x = (uint32_t)f2bf(v[0]) | ((uint32_t)f2bf(v[1]) << 16);
               q.y = (uint32_t)f2bf(v[2]) | ((uint32_t)f2bf(v[3]) << 16);
@@ -702,9 +710,9 @@ static int launch_block_v(const BlockConvArgs& a, int v, hipStream_t s) {
     case 10: return launch_block_t<T, 2, 2, 4, 4, 2, 2, false, X3>(a, s);
     case 11: return launch_block_t<T, 1, 4, 4, 4, 3, 1, false, X3>(a, s);
     case 12: return launch_block_t<T, 2, 2, 4, 4, 3, 1, false, X3>(a, s);
-    case 13: return launch_block_t<T, 2, 4, 8, 4, 2, 1, true, X3, sizeof(T) == 2 && !X3>(a, s);
+    case 13: return launch_block_t<T, 2, 4, 8, 4, 2, 1, true, X3, std::is_same<T, u16>::value && !X3>(a, s);
     case 14: return launch_block_t<T, 2, 4, 4, 4, 2, 1, false, X3>(a, s);
-    case 15: return launch_block_t<T, 2, 4, 4, 4, 3, 1, false, X3, sizeof(T) == 2 && !X3>(a, s);
+    case 15: return launch_block_t<T, 2, 4, 4, 4, 3, 1, false, X3, std::is_same<T, u16>::value && !X3>(a, s);
     case 16: return launch_block_t<T, 1, 8, 4, 4, 2, 1, false, X3>(a, s);
     case 17: return launch_block_t<T, 2, 2, 8, 4, 2, 1, false, X3>(a, s);
     case 18: return launch_block_t<T, 2, 2, 4, 8, 2, 1, false, X3>(a, s);
@@ -725,17 +733,17 @@ static int launch_block_x4(const BlockConvArgs& a, int v, hipStream_t s) {
   return SAD_ERR_ARG;
 }
 
-int launch_halo_v(const BlockConvArgs& a, int v, hipStream_t s, bool x3 = false);
+int launch_halo_v(const BlockConvArgs& a, int v, hipStream_t s, bool x3 = false, bool h16 = false);
 int launch_halo256(const BlockConvArgs& a, hipStream_t s, bool x3);
-int launch_halo256r(const BlockConvArgs& a, hipStream_t s, bool x3);
+int launch_halo256r(const BlockConvArgs& a, hipStream_t s, bool x3, bool h16 = false);
 bool halo256_ok(const BlockConvArgs& a);
-int launch_halo_rw(const BlockConvArgs& a, hipStream_t s);
-int launch_l2conv(const BlockConvArgs& a, hipStream_t s, bool x3 = false);
+int launch_halo_rw(const BlockConvArgs& a, hipStream_t s, bool h16 = false);
+int launch_l2conv(const BlockConvArgs& a, hipStream_t s, bool x3 = false, bool h16 = false);
 int launch_halo256s2(const BlockConvArgs& a, hipStream_t s);
 bool halo256s2_ok(const BlockConvArgs& a);
 int launch_halo_rw_x3(const BlockConvArgs& a, hipStream_t s);
-int launch_l2s2conv(const BlockConvArgs& a, hipStream_t s);
-int launch_halo256rs2(const BlockConvArgs& a, hipStream_t s, bool x3);
+int launch_l2s2conv(const BlockConvArgs& a, hipStream_t s, bool h16 = false);
+int launch_halo256rs2(const BlockConvArgs& a, hipStream_t s, bool x3, bool h16 = false);
 bool halo256rs2_ok(const BlockConvArgs& a);
 
 // halo kernel (variant 20): bf16 stride-1 3x3 with Cout <= 128 (layer1, layer2's
@@ -745,7 +753,7 @@ bool halo256rs2_ok(const BlockConvArgs& a);
 // for any Cout (variants 13, 31 and 41 take it for theirs).
 // (split-bf16: logical channels; the kernel sees 2 Cin bf16 channels)
 static bool halo_ok(const BlockConvArgs& a, int dtype) {
-  return (dtype == SAD_BF16 || dtype == SAD_BF16X3) && a.KH == 3 && a.KW == 3 && a.stride == 1 && a.pad == 1 &&
+  return (is16(dtype) || dtype == SAD_BF16X3) && a.KH == 3 && a.KW == 3 && a.stride == 1 && a.pad == 1 &&
          !a.in1 && a.Cin % (dtype == SAD_BF16X3 ? 32 : 64) == 0 && a.Cout % 64 == 0 && a.W % 16 == 0 &&
          a.H % 16 == 0;
 }
@@ -767,7 +775,7 @@ static bool layer2_v31() {
 // shortcut source beside it
 static bool halo31_ok(const BlockConvArgs& a, int dtype) {
   return a.KH == 3 && a.KW == 3 && a.stride == 1 && a.pad == 1 && a.Cout % 128 == 0 && a.H % 16 == 0 &&
-         a.W % 16 == 0 && a.Ho == a.H && a.Wo == a.W && (!a.res || (dtype == SAD_BF16 && !a.in1)) && !a.st_part &&
+         a.W % 16 == 0 && a.Ho == a.H && a.Wo == a.W && (!a.res || (is16(dtype) && !a.in1)) && !a.st_part &&
          a.Cin % 64 == 0 && (!a.in1 || a.Cin1 % 64 == 0) &&
          (!a.pool_out || (a.H == 16 && a.W == 16 && a.Cout % 256 == 0));
 }
@@ -896,7 +904,7 @@ static int halo256_mode() {
 // to their kernels, when variant 31 runs these convs at all (SAD_HALO256 = 2,
 // the default; 0 / 1 keep the identity as K columns on variants 13 / 30)
 static bool v31_identity_residual(int dtype, int cout, int Ho) {
-  return dtype == SAD_BF16 && halo256_mode() == 2 && cout % 256 == 0 && Ho % 16 == 0;
+  return is16(dtype) && halo256_mode() == 2 && cout % 256 == 0 && Ho % 16 == 0;
 }
 // Does conv2 of this identity BasicBlock take its shortcut as the epilogue
 // residual `res` (true) or as identity K columns over `in1` (false)?  The
@@ -912,9 +920,9 @@ static bool v31_identity_residual(int dtype, int cout, int Ho) {
 // The weights keep their layout either way: with `res` the identity's K columns
 // are not read.
 bool identity_shortcut_is_res(int dtype, int x4, int cin, int cout, int stride, bool has_ds, int Ho) {
-  if (x4 || !(dtype == SAD_BF16 || dtype == SAD_BF16X3) || stride != 1 || has_ds || cin != cout || Ho % 16 != 0)
+  if (x4 || !(is16(dtype) || dtype == SAD_BF16X3) || stride != 1 || has_ds || cin != cout || Ho % 16 != 0)
     return false;
-  return cout <= 64 || (cout <= 128 && layer2_halo() && !(dtype == SAD_BF16 && layer2_v31()) &&
+  return cout <= 64 || (cout <= 128 && layer2_halo() && !(is16(dtype) && layer2_v31()) &&
                         !(dtype == SAD_BF16X3 && x3_layer2_v31())) ||
          v31_identity_residual(dtype, cout, Ho);
 }
@@ -946,20 +954,24 @@ int default_block_variant(const BlockConvArgs& a, int dtype) {
     if (x3_s2_variant() == 44 && halo256rs2_ok(a) && a.Cout % 256 == 0) return 44;
     return halo_ok(a, dtype) && a.Cout <= 128 ? 20 : (a.Cout % 256 == 0 ? 13 : (a.Cout % 128 == 0 ? c128_variant() : 9));
   }
+  // fp16 (SAD_F16) takes bf16's choice everywhere but on the two A/B switches
+  // SAD_HALO256=1 (variant 30) and SAD_S2_PATCH=1 (variant 32), which are
+  // bf16 only: it runs the implicit GEMM there
+  const bool bf = dtype == SAD_BF16;
   if (halo_ok(a, dtype) && a.Cin == 64 && a.Cout == 64) return 25;  // layer1: resident weights
   // layer2's second block (128 -> 128, stride 1, identity as an epilogue
   // residual): the resident-weight conv (variant 41)
-  if (dtype == SAD_BF16 && l2_rw() && halo_ok(a, dtype) && a.Cin == 128 && a.Cout == 128 && !a.st_part) return 41;
+  if (is16(dtype) && l2_rw() && halo_ok(a, dtype) && a.Cin == 128 && a.Cout == 128 && !a.st_part) return 41;
   // layer2's first block, conv2 + the downsample (its 1x1/2 of the 64-channel
   // block input as two more K-steps): the same kernel
-  if (dtype == SAD_BF16 && l2_ds_rw() && l2conv_ds_ok(a)) return 41;
+  if (is16(dtype) && l2_ds_rw() && l2conv_ds_ok(a)) return 41;
   // layer2's 128-channel stride-1 convs (incl. conv2 + downsample / identity as
   // shortcut columns): variant 31 with 128-channel tiles
-  if (dtype == SAD_BF16 && layer2_v31() && a.Cout == 128 && !a.res && halo31_ok(a, dtype)) return 31;
+  if (is16(dtype) && layer2_v31() && a.Cout == 128 && !a.res && halo31_ok(a, dtype)) return 31;
   // layer3/4's identity blocks (identity_shortcut_is_res):
   // variant 31 with the shortcut as an epilogue residual -- before the halo
   // kernel's line below, and whatever the batch size (see the layer3/4 choice)
-  if (dtype == SAD_BF16 && halo256_mode() == 2 && a.res && a.Cout % 256 == 0 && halo31_ok(a, dtype)) return 31;
+  if (is16(dtype) && halo256_mode() == 2 && a.res && a.Cout % 256 == 0 && halo31_ok(a, dtype)) return 31;
   if (halo_ok(a, dtype) && (a.res || (a.Cout <= 128 && layer2_halo())))
     return a.Cout == 128 && !a.res && halo_c128_variant() == 22 ? 22 : 20;
   // layer3/4 stride-1 convs: the patch-resident kernels (bf16 only: the fp32
@@ -967,13 +979,14 @@ int default_block_variant(const BlockConvArgs& a, int dtype) {
   // 13/15, and a batch-size-dependent switch would make results depend on the
   // micro-batch (a 1-rank and a 2-rank run of the same segments must agree
   // bit for bit)
-  if (dtype == SAD_BF16 && halo256_mode() != 0 && halo256_ok(a)) return halo256_mode() == 2 ? 31 : 30;
+  if (bf && halo256_mode() != 0 && halo256_ok(a)) return halo256_mode() == 2 ? 31 : 30;
+  if (dtype == SAD_F16 && halo256_mode() == 2 && halo256_ok(a)) return 31;
   // layer2's stride-2 conv1 (64 -> 128): resident weights (variant 43; chosen
   // whatever the grid size: its K order differs from variant 15's)
-  if (dtype == SAD_BF16 && l2s2_rw() && l2s2_ok(a)) return 43;
+  if (is16(dtype) && l2s2_rw() && l2s2_ok(a)) return 43;
   // the stride-2 3x3 convs: the patch-resident variant 32 (chosen whatever the
   // grid size, as above)
-  if (dtype == SAD_BF16 && s2_patch() == 2 && halo256rs2_ok(a)) return 44;
+  if (is16(dtype) && s2_patch() == 2 && halo256rs2_ok(a)) return 44;
   if (dtype == SAD_BF16 && s2_patch() == 1 && halo256s2_ok(a)) return 32;
   return gemm_block_variant(a);
 }
@@ -1084,8 +1097,9 @@ static thread_local int64_t g_block_conv_kernels = 0;
 int64_t block_conv_kernel_launches() { return g_block_conv_kernels; }
 
 int launch_block_conv(const BlockConvArgs& a_in, int dtype, hipStream_t s, int variant) {
-  SAD_REQUIRE(dtype == SAD_F32 || dtype == SAD_BF16 || dtype == SAD_BF16X3, "dtype");
+  SAD_REQUIRE(dtype == SAD_F32 || dtype == SAD_BF16 || dtype == SAD_BF16X3 || dtype == SAD_F16, "dtype");
   const int ES = dtype == SAD_F32 ? 4 : 2;
+  const bool h16 = dtype == SAD_F16;
   BlockConvArgs a = a_in;
   if (dtype == SAD_BF16X3) {
     // callers count logical channels; the kernel sees the split layout's bf16
@@ -1155,7 +1169,7 @@ int launch_block_conv(const BlockConvArgs& a_in, int dtype, hipStream_t s, int v
               "four-product convs: split-bf16 inference on variants 9 / 13 / 15, no fused statistics or pool");
   ++g_block_conv_kernels;
   if (v == 30) {
-    SAD_REQUIRE(dtype != SAD_F32 && halo256_ok(a_in), "variant 30: bf16 / split-bf16 3x3/s1/p1, Cout % 256, 16 x 16 tiles");
+    SAD_REQUIRE(dtype != SAD_F32 && !h16 && halo256_ok(a_in), "variant 30: bf16 / split-bf16 3x3/s1/p1, Cout % 256, 16 x 16 tiles");
 #if SAD_STAMPS
     static uint64_t* stamp_buf30 = nullptr;
     if (!stamp_this_launch(1)) return launch_halo256(a, s, dtype == SAD_BF16X3);
@@ -1169,27 +1183,27 @@ int launch_block_conv(const BlockConvArgs& a_in, int dtype, hipStream_t s, int v
 #endif
   }
   if (v == 31) {
-    SAD_REQUIRE((dtype == SAD_BF16 || dtype == SAD_BF16X3) && halo31_ok(a_in, dtype),
-                "variant 31: bf16 / split-bf16 3x3/s1/p1, Cout % 128, 16 x 16 tiles; epilogue residual in bf16 only, "
-                "without a shortcut source");
-    return launch_halo256r(a, s, dtype == SAD_BF16X3);
+    SAD_REQUIRE((is16(dtype) || dtype == SAD_BF16X3) && halo31_ok(a_in, dtype),
+                "variant 31: bf16 / fp16 / split-bf16 3x3/s1/p1, Cout % 128, 16 x 16 tiles; epilogue residual in bf16 "
+                "and fp16 only, without a shortcut source");
+    return launch_halo256r(a, s, dtype == SAD_BF16X3, h16);
   }
   if (v == 32) {
     SAD_REQUIRE(dtype == SAD_BF16, "variant 32: bf16");
     return launch_halo256s2(a, s);
   }
   if (v == 44) {
-    SAD_REQUIRE((dtype == SAD_BF16 || dtype == SAD_BF16X3) && halo256rs2_ok(a_in),
-                "variant 44: bf16 / split-bf16 3x3/s2/p1, Cin % 64, Cout % 128, 16 x 16 output tiles");
-    return launch_halo256rs2(a, s, dtype == SAD_BF16X3);
+    SAD_REQUIRE((is16(dtype) || dtype == SAD_BF16X3) && halo256rs2_ok(a_in),
+                "variant 44: bf16 / fp16 / split-bf16 3x3/s2/p1, Cin % 64, Cout % 128, 16 x 16 output tiles");
+    return launch_halo256rs2(a, s, dtype == SAD_BF16X3, h16);
   }
   if (v == 41) {
-    SAD_REQUIRE(dtype == SAD_BF16 && (halo_ok(a_in, dtype) || l2conv_ds_ok(a_in)), "variant 41: bf16 3x3/s1/p1, H, W % 16");
-    return launch_l2conv(a, s);
+    SAD_REQUIRE(is16(dtype) && (halo_ok(a_in, dtype) || l2conv_ds_ok(a_in)), "variant 41: bf16 / fp16 3x3/s1/p1, H, W % 16");
+    return launch_l2conv(a, s, false, h16);
   }
   if (v == 43) {
-    SAD_REQUIRE(dtype == SAD_BF16 && l2s2_ok(a_in), "variant 43: bf16 64 -> 128 3x3/s2/p1, output H, W % 16");
-    return launch_l2s2conv(a, s);
+    SAD_REQUIRE(is16(dtype) && l2s2_ok(a_in), "variant 43: bf16 / fp16 64 -> 128 3x3/s2/p1, output H, W % 16");
+    return launch_l2s2conv(a, s, h16);
   }
   if (v == 42) {
     SAD_REQUIRE(dtype == SAD_BF16X3 && halo_ok(a_in, dtype) && a_in.Cin == 64 && a_in.Cout == 64,
@@ -1205,22 +1219,22 @@ int launch_block_conv(const BlockConvArgs& a_in, int dtype, hipStream_t s, int v
     return launch_halo_v(a, v, s, true);
   }
   if (v == 25) {
-    SAD_REQUIRE(halo_ok(a, dtype), "halo conv (variant 25): bf16, 3x3/s1/p1, no GEMM shortcut, H, W % 16");
+    SAD_REQUIRE(halo_ok(a, dtype), "halo conv (variant 25): bf16 / fp16, 3x3/s1/p1, no GEMM shortcut, H, W % 16");
 #if SAD_STAMPS
     static uint64_t* stamp_buf25 = nullptr;
-    if (!stamp_this_launch(0)) return launch_halo_rw(a, s);
+    if (!stamp_this_launch(0)) return launch_halo_rw(a, s, h16);
     if (!stamp_buf25) SAD_CHECK_HIP(hipMalloc(&stamp_buf25, kStampWords * 8));
     SAD_CHECK_HIP(hipMemsetAsync(stamp_buf25, 0, kStampWords * 8, s));
     a.stamps = stamp_buf25;
-    const int rc25 = launch_halo_rw(a, s);
+    const int rc25 = launch_halo_rw(a, s, h16);
     return rc25 == SAD_OK ? stamp_report(a, s) : rc25;
 #else
-    return launch_halo_rw(a, s);
+    return launch_halo_rw(a, s, h16);
 #endif
   }
   if (v == 20 || v == 21 || v == 22) {
-    SAD_REQUIRE(halo_ok(a, dtype), "halo conv (variants 20-22): bf16, 3x3/s1/p1, no GEMM shortcut, H, W % 16");
-    return launch_halo_v(a, v, s);
+    SAD_REQUIRE(halo_ok(a, dtype), "halo conv (variants 20-22): bf16 / fp16, 3x3/s1/p1, no GEMM shortcut, H, W % 16");
+    return launch_halo_v(a, v, s, false, h16);
   }
   SAD_REQUIRE(!a.res || a.res_pstride % 4 == 0, "residual pixel stride must keep 4-channel alignment");
 #if SAD_STAMPS
@@ -1238,7 +1252,8 @@ int launch_block_conv(const BlockConvArgs& a_in, int dtype, hipStream_t s, int v
     SAD_REQUIRE(v >= 9 && v <= 19, "split-bf16 runs on the implicit-GEMM variants 9..19");
     rc = launch_block_v<u16, true>(a, v, s);
   } else {
-    rc = dtype == SAD_BF16 ? launch_block_v<u16>(a, v, s) : launch_block_v<float>(a, v, s);
+    rc = h16 ? launch_block_v<f16>(a, v, s)
+             : dtype == SAD_BF16 ? launch_block_v<u16>(a, v, s) : launch_block_v<float>(a, v, s);
   }
 #if SAD_STAMPS
   if (rc == SAD_OK && a.stamps) rc = stamp_report(a, s);

@@ -5,6 +5,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include <string>
+#include <type_traits>
 
 #include "../../include/sad.h"
 
@@ -53,6 +54,73 @@ __device__ __forceinline__ u16 f2bf(float f) {
   return __builtin_bit_cast(u16, b);
 }
 __device__ __forceinline__ float bf2f(u16 h) { return __uint_as_float(((uint32_t)h) << 16); }
+
+// ---- the 16-bit element formats.  The kernels' element type E (or T) is u16
+// for bf16 and f16 for IEEE binary16 (SAD_F16): same bytes, same layouts, same
+// MFMA shape; what differs is the MFMA's type, the packing and the unpacking.
+typedef _Float16 f16;
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+template <typename E>
+constexpr bool is_f16_v = std::is_same<E, f16>::value;
+constexpr float F16_MAX = 65504.f;
+inline bool is16(int dtype) { return dtype == SAD_BF16 || dtype == SAD_F16; }  // 2-byte plain layouts
+inline int dtype_bytes(int dtype) { return is16(dtype) ? 2 : 4; }             // (split-bf16: 4 B per value)
+// host fp32 -> fp16 round-to-nearest-even (the plans refuse what would overflow)
+inline u16 f2h_host(float f) {
+  const _Float16 h = (_Float16)f;
+  u16 u;
+  __builtin_memcpy(&u, &h, 2);
+  return u;
+}
+// fp16 stores saturate: a finite value past +-65504 is stored as +-65504, never
+// as inf.  Every kernel that stores fp16 sets the wave's fp16-overflow clamp
+// mode (MODE.FP16_OVFL) once at entry: v_cvt_pk_f16_f32 / v_cvt_f16_f32 then
+// clamp an overflowing result themselves, at no cost per value (a v_med3_f32
+// per value in front of the conversion cost 1.0 % of the fp16 step:
+// profiles/fp16_sat_ab.txt).  The mode keeps a true infinity: an
+// fp32 value that is already inf or NaN is stored as such, which finite inputs
+// and the plans' weight check rule out (65504^2 K is far inside fp32).
+template <typename E>
+__device__ __forceinline__ void f16_kernel_entry() {
+  if constexpr (is_f16_v<E>) __builtin_amdgcn_s_setreg(1 | (23 << 6), 1);  // hwreg(HW_REG_MODE, 23, 1): FP16_OVFL
+}
+// float -> 16-bit element (RNE; fp16 saturating) and back
+template <typename E>
+__device__ __forceinline__ u16 to16(float f) {
+  if constexpr (is_f16_v<E>)
+    return __builtin_bit_cast(u16, (_Float16)f);
+  else
+    return f2bf(f);
+}
+template <typename E>
+__device__ __forceinline__ float from16(u16 h) {
+  if constexpr (is_f16_v<E>)
+    return (float)__builtin_bit_cast(_Float16, h);
+  else
+    return bf2f(h);
+}
+// two floats -> one packed fp16 pair: v_cvt_pk_f16_f32 (RNE, saturating under f16_kernel_entry)
+__device__ __forceinline__ uint32_t pk_f16(float lo, float hi) {
+  return __builtin_bit_cast(uint32_t, __builtin_convertvector((f32x2){lo, hi}, f16x2));
+}
+// the halves of a packed pair as floats, one VALU each: bf16 is a shift / a
+// mask; fp16 is v_cvt_f32_f16 (the high half through SDWA WORD_1)
+template <typename E>
+__device__ __forceinline__ float lo16(uint32_t q) {
+  if constexpr (is_f16_v<E>)
+    return (float)__builtin_bit_cast(f16x2, q)[0];
+  else
+    return __uint_as_float(q << 16);
+}
+template <typename E>
+__device__ __forceinline__ float hi16(uint32_t q) {
+  if constexpr (is_f16_v<E>)
+    return (float)__builtin_bit_cast(f16x2, q)[1];
+  else
+    return __uint_as_float(q & 0xFFFF0000u);
+}
 
 // torchvision bilinear sample (align_corners=False, source index clamped at 0;
 // the antialias filter reduces to this for upsampling) of an `in`-long axis at

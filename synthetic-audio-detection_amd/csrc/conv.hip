@@ -53,6 +53,7 @@ __global__ __launch_bounds__(64 * WM * WN, 1) void conv_igemm_kernel(ConvArgs a)
   constexpr int NT = 64 * NW;               // threads
   constexpr int BM = 64 * WM, BN = 64 * WN;
   constexpr int ES = sizeof(T);
+  f16_kernel_entry<T>();
   if (blockIdx.y > 0) {  // grouped launch: this group's operands (uniform)
     const int g = blockIdx.y;
     a.in = (const T*)a.in + g * a.in_gstride;
@@ -216,7 +217,7 @@ __global__ __launch_bounds__(64 * WM * WN, 1) void conv_igemm_kernel(ConvArgs a)
         const uint4 q = *(const uint4*)rp;
         const u16* h = (const u16*)&q;
 #pragma unroll
-        for (int e = 0; e < 8; ++e) v[e] += bf2f(h[e]);
+        for (int e = 0; e < 8; ++e) v[e] += from16<T>(h[e]);
       } else {
         const float4 q0 = *(const float4*)rp, q1 = *(const float4*)(rp + 4);
         v[0] += q0.x; v[1] += q0.y; v[2] += q0.z; v[3] += q0.w;
@@ -232,7 +233,7 @@ __global__ __launch_bounds__(64 * WM * WN, 1) void conv_igemm_kernel(ConvArgs a)
       uint4 q;
       u16* h = (u16*)&q;
 #pragma unroll
-      for (int e = 0; e < 8; ++e) h[e] = f2bf(v[e]);
+      for (int e = 0; e < 8; ++e) h[e] = to16<T>(v[e]);
       *(uint4*)op = q;
     } else {
       *(float4*)op = make_float4(v[0], v[1], v[2], v[3]);
@@ -472,10 +473,12 @@ __device__ __forceinline__ int stem_oswz(int q) { return ((q & 1) << 2) | (q & 2
 // two floats -> packed bf16 pair (RNE): one v_cvt_pk_bf16_f32
 typedef __bf16 stem_bf2 __attribute__((ext_vector_type(2)));
 typedef float stem_f2 __attribute__((ext_vector_type(2)));
+template <typename E = u16>
 __device__ __forceinline__ uint32_t stem_pk(float lo, float hi) {
+  if constexpr (is_f16_v<E>) return pk_f16(lo, hi);
   return __builtin_bit_cast(uint32_t, __builtin_convertvector((stem_f2){lo, hi}, stem_bf2));
 }
-// ReLU of a packed bf16 pair (as int16 negative bf16 values are negative)
+// ReLU of a packed bf16 (or fp16) pair (as int16 negative values are negative)
 __device__ __forceinline__ uint32_t stem_relu2(uint32_t x) {
   uint32_t r;
   asm("v_pk_max_i16 %0, %1, 0" : "=v"(r) : "v"(x));
@@ -512,11 +515,15 @@ constexpr int stem_u_floats() {
 // owns (2*py0 .. 2*py0 + 2P - 1; the carry-in row belongs to the previous one)
 // feeds per-channel sums of y and y^2 -> a.part[workgroup][2][64] (the
 // bn_reduce_kernel partial format) for the batch statistics.
-template <bool X3, bool TRAIN = false, bool X4 = false>
+// E = f16 (SAD_F16): the same kernel with the band, the weights and the output
+// in fp16 (f16 MFMA, v_cvt_pk_f16_f32, saturating stores)
+template <bool X3, bool TRAIN = false, bool X4 = false, typename E = u16>
 __global__ __launch_bounds__(256, X3 ? 1 : 2) void stem_bf16_kernel(StemArgs a) {
   static_assert(!(X3 && TRAIN), "the training stem is bf16");
+  static_assert(!is_f16_v<E> || (!X3 && !TRAIN), "the fp16 stem is the plain inference form");
   static_assert(!X4 || X3, "X4: the split stem's fourth product");
   constexpr int OPITCH = X3 ? STEM_OPITCH_X3 : STEM_OPITCH;
+  f16_kernel_entry<E>();
   __shared__ __attribute__((aligned(16))) u16 s_img[STEM_BAND_ROWS * STEM_BPITCH];
   __shared__ __attribute__((aligned(16))) u16 s_imgl[X3 ? STEM_BAND_ROWS * STEM_BPITCH : 8];
   __shared__ __attribute__((aligned(16))) u16 s_w[64 * STEM_WPITCH];
@@ -541,7 +548,7 @@ __global__ __launch_bounds__(256, X3 ? 1 : 2) void stem_bf16_kernel(StemArgs a) 
   }
   // band element store: bf16, or the hi/lo pair
   auto put = [&](int i, float v) __attribute__((always_inline)) {
-    const u16 h = f2bf(v);
+    const u16 h = to16<E>(v);
     s_img[i] = h;
     if constexpr (X3) s_imgl[i] = f2bf(v - bf2f(h));
   };
@@ -652,7 +659,7 @@ __global__ __launch_bounds__(256, X3 ? 1 : 2) void stem_bf16_kernel(StemArgs a) 
                             w0 * u0.w + w1 * u1.w};
         u16 h[4];
 #pragma unroll
-        for (int e = 0; e < 4; ++e) h[e] = f2bf(v[e]);
+        for (int e = 0; e < 4; ++e) h[e] = to16<E>(v[e]);
         const int o = tr * STEM_BPITCH + 4 * q;
         *(uint2*)(s_img + o) = make_uint2((uint32_t)h[0] | ((uint32_t)h[1] << 16), (uint32_t)h[2] | ((uint32_t)h[3] << 16));
         if constexpr (X3) {
@@ -708,10 +715,16 @@ __global__ __launch_bounds__(256, X3 ? 1 : 2) void stem_bf16_kernel(StemArgs a) 
         av.z = *(const uint32_t*)(p + 4);
         av.w = *(const uint32_t*)(p + 6);
 #pragma unroll
-        for (int j = 0; j < 4; ++j)  // C[px][ch]
+        for (int j = 0; j < 4; ++j) {  // C[px][ch]
+          if constexpr (is_f16_v<E>)
+            r[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, av),
+                                                             __builtin_bit_cast(f16x8, bw[j][s]),
+                                                             s == 0 ? init[j] : r[i][j], 0, 0, 0);
+          else
           r[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, av),
                                                             __builtin_bit_cast(bf16x8, bw[j][s]),
                                                             s == 0 ? init[j] : r[i][j], 0, 0, 0);
+        }
         if constexpr (X3) {
           const u16* pl = s_imgl + o;
           uint4 al;
@@ -820,8 +833,8 @@ __global__ __launch_bounds__(256, X3 ? 1 : 2) void stem_bf16_kernel(StemArgs a) 
           // plus the bias, packed as one bf16 pair, ReLU on the
           // pair (int16 max), then lanes (c, c^1) trade pairs (one DPP) and a
           // byte permute forms (c0, c0+1) of q0 (even lanes) / q0+1 (odd)
-          const uint32_t pq = stem_relu2(stem_pk(fmaxf(fmaxf(left, x[0]), x[1]) + bias[j],
-                                                 fmaxf(fmaxf(x[1], x[2]), x[3]) + bias[j]));
+          const uint32_t pq = stem_relu2(stem_pk<E>(fmaxf(fmaxf(left, x[0]), x[1]) + bias[j],
+                                                    fmaxf(fmaxf(x[1], x[2]), x[3]) + bias[j]));
           const uint32_t pn = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)pq, 0xB1, 0xF, 0xF, true);  // quad_perm 1,0,3,2
           const uint32_t w = __builtin_amdgcn_perm(pn, pq, even ? 0x05040100u : 0x03020706u);
           const int q = wave * 32 + i * 8 + 2 * fg + (even ? 0 : 1);
@@ -910,7 +923,7 @@ __global__ __launch_bounds__(256, X3 ? 1 : 2) void stem_bf16_kernel(StemArgs a) 
 // 148-151); the spectrogram path's three channels are identical and take the
 // folded MFMA stems above.  Not the hot path: one workgroup per pooled row,
 // one thread per pooled pixel, weights broadcast from LDS.
-// OUT: 0 fp32, 1 bf16, 2 split-bf16 ([hi 32 | lo 32] per 32 channels)
+// OUT: 0 fp32, 1 bf16, 2 split-bf16 ([hi 32 | lo 32] per 32 channels), 3 fp16
 constexpr int STEM3_PITCH = 520;  // band columns ix + 5 in [0, 519)
 template <int OUT>
 __global__ __launch_bounds__(128) void stem3_kernel(StemArgs a) {
@@ -919,6 +932,7 @@ __global__ __launch_bounds__(128) void stem3_kernel(StemArgs a) {
   const int tid = threadIdx.x;
   const int py = blockIdx.x;
   const int64_t b = blockIdx.y;
+  if constexpr (OUT == 3) f16_kernel_entry<f16>();
   for (int i = tid; i < 64 * 147; i += 128) s_w[(i / 147) * 148 + i % 147] = a.w3[i];
   const float* img = a.img3 + b * 3 * 512 * 512;
   for (int i = tid; i < 3 * STEM_IMG_ROWS * STEM3_PITCH; i += 128) {
@@ -972,6 +986,10 @@ __global__ __launch_bounds__(128) void stem3_kernel(StemArgs a) {
     u16* o = (u16*)a.out + pix * 64;
 #pragma unroll
     for (int j = 0; j < 64; ++j) o[j] = f2bf(pooled[j]);
+  } else if constexpr (OUT == 3) {
+    u16* o = (u16*)a.out + pix * 64;
+#pragma unroll
+    for (int j = 0; j < 64; ++j) o[j] = to16<f16>(pooled[j]);
   } else {
     u16* o = (u16*)a.out + pix * 128;
 #pragma unroll
@@ -1000,6 +1018,8 @@ __global__ __launch_bounds__(256) void avgpool_kernel(const T* __restrict__ in, 
   for (int i = g; i < hw; i += 4) {
     if constexpr (X3)
       s += bf2f(p[(int64_t)i * ps]) + bf2f(p[(int64_t)i * ps + 32]);
+    else if constexpr (is_f16_v<T>)
+      s += (float)p[(int64_t)i * c];
     else if constexpr (sizeof(T) == 2)
       s += bf2f(p[(int64_t)i * c]);
     else
@@ -1065,15 +1085,15 @@ static int64_t conv_in_bytes(int64_t pixels, int64_t in_pstride, int Cin, int ES
 }
 
 int64_t conv_max_pixels(int64_t in_pstride, int Cin, int dtype) {
-  const int ES = dtype == SAD_BF16 ? 2 : 4;
+  const int ES = dtype_bytes(dtype);
   // largest P with conv_in_bytes(P) < CONV_IN_LIMIT
   const int64_t room = (CONV_IN_LIMIT - 1) / ES - Cin;
   return room < 0 ? 0 : room / in_pstride + 1;
 }
 
 int launch_conv(const ConvArgs& a_in, int dtype, hipStream_t s, int variant) {
-  const int EPC = dtype == SAD_BF16 ? 8 : 4;
-  const int ES = dtype == SAD_BF16 ? 2 : 4;
+  const int EPC = is16(dtype) ? 8 : 4;
+  const int ES = dtype_bytes(dtype);
   ConvArgs a = a_in;
   a.in_bytes = conv_in_bytes((int64_t)a.N * a.H * a.W, a.in_pstride, a.Cin, ES);
   a.wt_bytes = (int64_t)a.Cout * a.KH * a.KW * a.Cin * ES;
@@ -1084,6 +1104,7 @@ int launch_conv(const ConvArgs& a_in, int dtype, hipStream_t s, int variant) {
   SAD_REQUIRE(a.in_pstride % EPC == 0 && a.out_pstride % 8 == 0, "pixel strides must keep 16-B alignment");
   if (a.M == 0) return SAD_OK;
   const int v = variant > 0 ? variant : default_conv_variant(a);
+  if (dtype == SAD_F16) return launch_conv_v<f16>(a, v, s);
   return dtype == SAD_BF16 ? launch_conv_v<u16>(a, v, s) : launch_conv_v<float>(a, v, s);
 }
 
@@ -1096,6 +1117,8 @@ int launch_stem(const StemArgs& a, int dtype, hipStream_t s) {
       hipLaunchKernelGGL(stem3_kernel<0>, dim3(128, (unsigned)a.B), dim3(128), 0, s, a);
     else if (dtype == SAD_BF16)
       hipLaunchKernelGGL(stem3_kernel<1>, dim3(128, (unsigned)a.B), dim3(128), 0, s, a);
+    else if (dtype == SAD_F16)
+      hipLaunchKernelGGL(stem3_kernel<3>, dim3(128, (unsigned)a.B), dim3(128), 0, s, a);
     else
       hipLaunchKernelGGL(stem3_kernel<2>, dim3(128, (unsigned)a.B), dim3(128), 0, s, a);
     SAD_CHECK_HIP(hipGetLastError());
@@ -1103,6 +1126,9 @@ int launch_stem(const StemArgs& a, int dtype, hipStream_t s) {
   }
   if (dtype == SAD_BF16)
     hipLaunchKernelGGL(stem_bf16_kernel<false>, dim3(128 / STEM_P, (unsigned)a.B), dim3(256), 0, s, a);
+  else if (dtype == SAD_F16)
+    hipLaunchKernelGGL((stem_bf16_kernel<false, false, false, f16>), dim3(128 / STEM_P, (unsigned)a.B), dim3(256), 0, s,
+                       a);
   else if (dtype == SAD_BF16X3 && a.x4)
     hipLaunchKernelGGL((stem_bf16_kernel<true, false, true>), dim3(128 / STEM_P, (unsigned)a.B), dim3(256), 0, s, a);
   else if (dtype == SAD_BF16X3)
@@ -1129,6 +1155,8 @@ int launch_avgpool(const void* in, int64_t B, int hw, int c, float* out, int dty
                        out);
   else if (dtype == SAD_BF16)
     hipLaunchKernelGGL(avgpool_kernel<u16>, dim3((unsigned)B, c / 64), dim3(256), 0, s, (const u16*)in, hw, c, out);
+  else if (dtype == SAD_F16)
+    hipLaunchKernelGGL(avgpool_kernel<f16>, dim3((unsigned)B, c / 64), dim3(256), 0, s, (const f16*)in, hw, c, out);
   else
     hipLaunchKernelGGL(avgpool_kernel<float>, dim3((unsigned)B, c / 64), dim3(256), 0, s, (const float*)in, hw, c, out);
   SAD_CHECK_HIP(hipGetLastError());

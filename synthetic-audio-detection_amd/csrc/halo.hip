@@ -105,8 +105,13 @@ struct HaloGeo {
 // tile's last chunk) and stores hi/lo from registers.
 // ST: training forward -- fused BN statistics of the conv output (StatAcc),
 // one [2][BC] row per pixel-group workgroup
-template <int WC, int WP, int TC, int TP, int TW, bool RES, bool RELU, bool X3 = false, bool ST = false>
+// E = f16 (SAD_F16): fp16 tensors in the plain inference forms (the f16 MFMA,
+// v_cvt_pk_f16_f32 stores, v_cvt_f32_f16 for the residual's halves)
+template <int WC, int WP, int TC, int TP, int TW, bool RES, bool RELU, bool X3 = false, bool ST = false,
+          typename E = u16>
 __global__ __launch_bounds__(64 * WC * WP, WC * WP / 4) void halo_conv_kernel(BlockConvArgs a) {
+  static_assert(!is_f16_v<E> || (!X3 && !ST), "fp16: the plain inference forms");
+  f16_kernel_entry<E>();
   using G = HaloGeo<WC, WP, TC, TP, TW, X3>;
   constexpr int NL = G::NL, BC = G::BC, TH = G::TH, PW = G::PW, PR = G::PR;
   constexpr int QP = G::QP, QR = G::QR, QW = G::QW, NDP = G::NDP, NWS = G::NWS;
@@ -273,15 +278,19 @@ __global__ __launch_bounds__(64 * WC * WP, WC * WP / 4) void halo_conv_kernel(Bl
           v[3] += __uint_as_float(h.y & 0xFFFF0000u) + __uint_as_float(l.y & 0xFFFF0000u);
         } else if constexpr (RES) {
           const uint2 h = xres[j][i][0];
-          v[0] += __uint_as_float(h.x << 16);
-          v[1] += __uint_as_float(h.x & 0xFFFF0000u);
-          v[2] += __uint_as_float(h.y << 16);
-          v[3] += __uint_as_float(h.y & 0xFFFF0000u);
+          v[0] += lo16<E>(h.x);
+          v[1] += hi16<E>(h.x);
+          v[2] += lo16<E>(h.y);
+          v[3] += hi16<E>(h.y);
         }
         if constexpr (RELU)
 #pragma unroll
           for (int r = 0; r < 4; ++r) v[r] = fmaxf(v[r], 0.f);
-        if constexpr (!X3) {  // plain bf16 (variant 22): one 8-B store per lane
+        if constexpr (is_f16_v<E>) {  // (variant 22 in fp16)
+          *(uint2*)(op + co) = make_uint2(pk_f16(v[0], v[1]), pk_f16(v[2], v[3]));
+          acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+          continue;
+        } else if constexpr (!X3) {  // plain bf16 (variant 22): one 8-B store per lane
           *(uint2*)(op + co) = make_uint2((uint32_t)f2bf(v[0]) | ((uint32_t)f2bf(v[1]) << 16),
                                           (uint32_t)f2bf(v[2]) | ((uint32_t)f2bf(v[3]) << 16));
           acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -335,17 +344,22 @@ __global__ __launch_bounds__(64 * WC * WP, WC * WP / 4) void halo_conv_kernel(Bl
         for (int r = 0; r < 4; ++r) v[r] = acc[i][j][r] + bias[i][r];
         if constexpr (RES) {
           const uint2 rv = rvs[j][i];
-          v[0] += __uint_as_float(rv.x << 16);
-          v[1] += __uint_as_float(rv.x & 0xFFFF0000u);
-          v[2] += __uint_as_float(rv.y << 16);
-          v[3] += __uint_as_float(rv.y & 0xFFFF0000u);
+          v[0] += lo16<E>(rv.x);
+          v[1] += hi16<E>(rv.x);
+          v[2] += lo16<E>(rv.y);
+          v[3] += hi16<E>(rv.y);
         }
         if constexpr (RELU)
 #pragma unroll
           for (int r = 0; r < 4; ++r) v[r] = fmaxf(v[r], 0.f);
         uint2 qv;
-        qv.x = (uint32_t)f2bf(v[0]) | ((uint32_t)f2bf(v[1]) << 16);
-        qv.y = (uint32_t)f2bf(v[2]) | ((uint32_t)f2bf(v[3]) << 16);
+        if constexpr (is_f16_v<E>) {
+          qv.x = pk_f16(v[0], v[1]);
+          qv.y = pk_f16(v[2], v[3]);
+        } else {
+          qv.x = (uint32_t)f2bf(v[0]) | ((uint32_t)f2bf(v[1]) << 16);
+          qv.y = (uint32_t)f2bf(v[2]) | ((uint32_t)f2bf(v[3]) << 16);
+        }
         *sp = qv;
         acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
       }
@@ -406,7 +420,7 @@ __global__ __launch_bounds__(64 * WC * WP, WC * WP / 4) void halo_conv_kernel(Bl
 #pragma unroll
       for (int i = 0; i < TC; ++i)
 #pragma unroll
-        for (int j = 0; j < TP; ++j) mfma_chunk<u16>(w[s][i], p[s][j], acc[i][j]);
+        for (int j = 0; j < TP; ++j) mfma_chunk<E>(w[s][i], p[s][j], acc[i][j]);
     }
     // schedule: half 0's reads, then its MFMAs interleaved with half 1's reads
     __builtin_amdgcn_sched_group_barrier(0x100, TC + TP, 0);
@@ -528,8 +542,11 @@ __global__ __launch_bounds__(64 * WC * WP, WC * WP / 4) void halo_conv_kernel(Bl
 // waves 0-3 run theirs before the tile barrier, waves 4-7 after it, so one
 // wave's VALU epilogue overlaps its partner's MFMAs instead of idling the
 // SIMD's matrix pipe.
-template <bool RES, bool RELU, bool ST = false>
+// E = f16 (SAD_F16): fp16 tensors in the inference forms.
+template <bool RES, bool RELU, bool ST = false, typename E = u16>
 __global__ __launch_bounds__(512, 1) void halo_rw_kernel(BlockConvArgs a) {
+  static_assert(!is_f16_v<E> || !ST, "fp16: the inference forms");
+  f16_kernel_entry<E>();
   constexpr int NW = 8, TC = 4, TP = 2, TW = 16, TH = 16;
   constexpr int PW = TW + 2, PR = PW * (TH + 2);  // 18 x 18 patch rows
   constexpr int NDP = (PR + 7) / 8;               // 41 DMA pieces per patch
@@ -642,17 +659,22 @@ __global__ __launch_bounds__(512, 1) void halo_rw_kernel(BlockConvArgs a) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) v[r] = acc[i][j][r] + bias[i][r];
         if constexpr (RES) {
-          v[0] += __uint_as_float(resv[i][j].x << 16);
-          v[1] += __uint_as_float(resv[i][j].x & 0xFFFF0000u);
-          v[2] += __uint_as_float(resv[i][j].y << 16);
-          v[3] += __uint_as_float(resv[i][j].y & 0xFFFF0000u);
+          v[0] += lo16<E>(resv[i][j].x);
+          v[1] += hi16<E>(resv[i][j].x);
+          v[2] += lo16<E>(resv[i][j].y);
+          v[3] += hi16<E>(resv[i][j].y);
         }
         if constexpr (RELU)
 #pragma unroll
           for (int r = 0; r < 4; ++r) v[r] = fmaxf(v[r], 0.f);
         uint2 q;
-        q.x = (uint32_t)f2bf(v[0]) | ((uint32_t)f2bf(v[1]) << 16);
-        q.y = (uint32_t)f2bf(v[2]) | ((uint32_t)f2bf(v[3]) << 16);
+        if constexpr (is_f16_v<E>) {
+          q.x = pk_f16(v[0], v[1]);
+          q.y = pk_f16(v[2], v[3]);
+        } else {
+          q.x = (uint32_t)f2bf(v[0]) | ((uint32_t)f2bf(v[1]) << 16);
+          q.y = (uint32_t)f2bf(v[2]) | ((uint32_t)f2bf(v[3]) << 16);
+        }
         *(uint2*)(op + i * 16) = q;  // (tap 0 of the next tile restarts acc from zero)
       }
     }
@@ -689,13 +711,18 @@ __global__ __launch_bounds__(512, 1) void halo_rw_kernel(BlockConvArgs a) {
         for (int j = 0; j < TP; ++j) {
           if constexpr (decltype(first)::value) {
             if (s == 0) {
+              if constexpr (is_f16_v<E>)
+                acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, wf[0][i]),
+                                                                   __builtin_bit_cast(f16x8, pf[0][j]),
+                                                                   f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
+              else
               acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, wf[0][i]),
                                                                   __builtin_bit_cast(bf16x8, pf[0][j]),
                                                                   f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
               continue;
             }
           }
-          mfma_chunk<u16>(wf[s][i], pf[s][j], acc[i][j]);
+          mfma_chunk<E>(wf[s][i], pf[s][j], acc[i][j]);
         }
   };
 
@@ -778,13 +805,13 @@ __global__ __launch_bounds__(512, 1) void halo_rw_kernel(BlockConvArgs a) {
   }
 }
 
-template <bool RES, bool RELU, bool ST = false>
+template <bool RES, bool RELU, bool ST = false, typename E = u16>
 static int launch_halo_rw_t(const BlockConvArgs& a, hipStream_t s) {
   constexpr int smem = 9 * 64 * 128 + 2 * 41 * 1024;
   static_assert(smem <= 160 * 1024, "LDS budget");
   static bool attr = false;
   if (!attr) {
-    (void)hipFuncSetAttribute((const void*)halo_rw_kernel<RES, RELU, ST>, hipFuncAttributeMaxDynamicSharedMemorySize,
+    (void)hipFuncSetAttribute((const void*)halo_rw_kernel<RES, RELU, ST, E>, hipFuncAttributeMaxDynamicSharedMemorySize,
                               smem);
     attr = true;
   }
@@ -800,12 +827,18 @@ static int launch_halo_rw_t(const BlockConvArgs& a, hipStream_t s) {
               "too large for one launch");
   const int64_t g = std::min<int64_t>(tiles_p, 256);
   if (ST) *a.st_rows = (int)g;
-  hipLaunchKernelGGL((halo_rw_kernel<RES, RELU, ST>), dim3((unsigned)g), dim3(512), smem, s, a);
+  hipLaunchKernelGGL((halo_rw_kernel<RES, RELU, ST, E>), dim3((unsigned)g), dim3(512), smem, s, a);
   SAD_CHECK_HIP(hipGetLastError());
   return SAD_OK;
 }
 
-int launch_halo_rw(const BlockConvArgs& a, hipStream_t s) {
+int launch_halo_rw(const BlockConvArgs& a, hipStream_t s, bool h16) {
+  if (h16) {
+    SAD_REQUIRE(!a.st_part, "variant 25: no fused statistics in fp16");
+    if (a.res)
+      return a.relu ? launch_halo_rw_t<true, true, false, f16>(a, s) : launch_halo_rw_t<true, false, false, f16>(a, s);
+    return a.relu ? launch_halo_rw_t<false, true, false, f16>(a, s) : launch_halo_rw_t<false, false, false, f16>(a, s);
+  }
   if (a.st_part) {
     SAD_REQUIRE(!a.res && !a.relu && a.st_rows, "fused BN statistics: raw conv (no residual / ReLU), st_rows set");
     return launch_halo_rw_t<false, false, true>(a, s);
@@ -1083,14 +1116,14 @@ int launch_halo_rw_x3(const BlockConvArgs& a, hipStream_t s) {
   return a.relu ? launch_halo_rw_x3_t<false, true>(a, s) : launch_halo_rw_x3_t<false, false>(a, s);
 }
 
-template <int WC, int WP, int TC, int TP, int TW, bool RES, bool RELU, bool X3, bool ST = false>
+template <int WC, int WP, int TC, int TP, int TW, bool RES, bool RELU, bool X3, bool ST = false, typename E = u16>
 static int launch_halo_t(const BlockConvArgs& a, hipStream_t s) {
   using G = HaloGeo<WC, WP, TC, TP, TW, X3>;
   static_assert(G::SMEM <= 160 * 1024, "LDS budget");
   static_assert(!ST || 2 * G::BC * WP * 4 <= 2 * G::PATCH, "statistics fold area");
   static bool attr = false;
   if (!attr) {
-    (void)hipFuncSetAttribute((const void*)halo_conv_kernel<WC, WP, TC, TP, TW, RES, RELU, X3, ST>,
+    (void)hipFuncSetAttribute((const void*)halo_conv_kernel<WC, WP, TC, TP, TW, RES, RELU, X3, ST, E>,
                               hipFuncAttributeMaxDynamicSharedMemorySize, G::SMEM);
     attr = true;
   }
@@ -1108,18 +1141,18 @@ static int launch_halo_t(const BlockConvArgs& a, hipStream_t s) {
   g = std::max<int64_t>(n_tc, g / n_tc * n_tc);
   if (X3) SAD_REQUIRE(a.out_pstride % 64 == 0 && (!a.res || a.res_pstride % 64 == 0), "split-bf16 pixel strides");
   if (ST) *a.st_rows = (int)(g / n_tc);
-  hipLaunchKernelGGL((halo_conv_kernel<WC, WP, TC, TP, TW, RES, RELU, X3, ST>), dim3((unsigned)g), dim3(64 * WC * WP),
+  hipLaunchKernelGGL((halo_conv_kernel<WC, WP, TC, TP, TW, RES, RELU, X3, ST, E>), dim3((unsigned)g), dim3(64 * WC * WP),
                      G::SMEM, s, a);
   SAD_CHECK_HIP(hipGetLastError());
   return SAD_OK;
 }
 
-template <int WC, int WP, int TC, int TP, int TW, bool X3 = false>
+template <int WC, int WP, int TC, int TP, int TW, bool X3 = false, typename E = u16>
 static int launch_halo_g(const BlockConvArgs& a, hipStream_t s) {
-  if (a.res) return a.relu ? launch_halo_t<WC, WP, TC, TP, TW, true, true, X3>(a, s)
-                           : launch_halo_t<WC, WP, TC, TP, TW, true, false, X3>(a, s);
-  return a.relu ? launch_halo_t<WC, WP, TC, TP, TW, false, true, X3>(a, s)
-                : launch_halo_t<WC, WP, TC, TP, TW, false, false, X3>(a, s);
+  if (a.res) return a.relu ? launch_halo_t<WC, WP, TC, TP, TW, true, true, X3, false, E>(a, s)
+                           : launch_halo_t<WC, WP, TC, TP, TW, true, false, X3, false, E>(a, s);
+  return a.relu ? launch_halo_t<WC, WP, TC, TP, TW, false, true, X3, false, E>(a, s)
+                : launch_halo_t<WC, WP, TC, TP, TW, false, false, X3, false, E>(a, s);
 }
 
 // Variants (channels x tile (TH x TW), waves, wave tile, LDS; one WG per CU):
@@ -1127,7 +1160,17 @@ static int launch_halo_g(const BlockConvArgs& a, hipStream_t s) {
 //  21: 64 x 16x16  4w  64x64  156 KB (one wave per SIMD: half the LDS fragment reads per MFMA)
 //  22: 128 x 16x16 8w  64x64  146 KB (Cout 128: one patch read per tile instead of two, a
 //      third fewer LDS fragment reads per MFMA than 20; 4-stage weight ring, register epilogue)
-int launch_halo_v(const BlockConvArgs& a, int v, hipStream_t s, bool x3) {
+int launch_halo_v(const BlockConvArgs& a, int v, hipStream_t s, bool x3, bool h16) {
+  if (h16) {  // bf16's instantiations, element type fp16
+    SAD_REQUIRE(!x3 && !a.st_part, "halo conv in fp16: the plain inference forms");
+    switch (v) {
+      case 20: return launch_halo_g<1, 8, 4, 2, 16, false, f16>(a, s);
+      case 21: return launch_halo_g<1, 4, 4, 4, 16, false, f16>(a, s);
+      case 22: return launch_halo_g<2, 4, 4, 4, 16, false, f16>(a, s);
+    }
+    set_error("unknown halo-conv variant");
+    return SAD_ERR_ARG;
+  }
   if (x3) {
     SAD_REQUIRE(v == 20, "split-bf16 halo conv: variant 20");
     return launch_halo_g<1, 8, 4, 2, 16, true>(a, s);

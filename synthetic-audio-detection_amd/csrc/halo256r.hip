@@ -69,7 +69,9 @@ typedef unsigned int h31_v4 __attribute__((ext_vector_type(4)));
 typedef __bf16 h31_bf2 __attribute__((ext_vector_type(2)));
 typedef float h31_f2 __attribute__((ext_vector_type(2)));
 // two floats -> packed bf16 pair (RNE): one v_cvt_pk_bf16_f32
+template <typename E = u16>
 __device__ __forceinline__ uint32_t h31_pk(float lo, float hi) {
+  if constexpr (is_f16_v<E>) return pk_f16(lo, hi);  // v_cvt_pk_f16_f32, saturating
   return __builtin_bit_cast(uint32_t, __builtin_convertvector((h31_f2){lo, hi}, h31_bf2));
 }
 // ReLU of a packed bf16 pair: as int16, negative bf16 values (and -0) are
@@ -92,8 +94,12 @@ __device__ __forceinline__ uint32_t h31_relu2(uint32_t x) {
 // shortcut: x is added in fp32 to the accumulators the wave already holds,
 // out = bf16(relu(acc + x)), the pooled form sums relu(acc + x)) -- its own
 // instantiations, so the launches without a residual do not carry its loads.
-template <int BC, bool POOL, bool X3 = false, bool RES = false>
+// E = f16 (SAD_F16): fp16 tensors -- the f16 MFMA, v_cvt_pk_f16_f32 with
+// saturation in the stores, v_cvt_f32_f16 for the residual's halves.
+template <int BC, bool POOL, bool X3 = false, bool RES = false, typename E = u16>
 __global__ __launch_bounds__(512, 1) void halo256r_kernel(BlockConvArgs a) {
+  static_assert(!is_f16_v<E> || !X3, "fp16 has no split form");
+  f16_kernel_entry<E>();
   using namespace h31;
   constexpr int NCG = BC / 32, NPG = NW / NCG, TP = 16 / NPG;
   static_assert(NCG * NPG == NW && (!POOL || NPG == 1), "wave split");
@@ -283,7 +289,7 @@ __global__ __launch_bounds__(512, 1) void halo256r_kernel(BlockConvArgs a) {
         for (int m = 0; m < NM; ++m)
 #pragma unroll
           for (int i = 0; i < TC; ++i)
-            mfma_chunk<u16>(__builtin_bit_cast(uint4, wv[i][X3 ? m : h]), bf[j], acc[i][j]);
+            mfma_chunk<E>(__builtin_bit_cast(uint4, wv[i][X3 ? m : h]), bf[j], acc[i][j]);
       // reads run 4 fragments ahead of the MFMAs that consume them
       __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);
 #pragma unroll
@@ -340,8 +346,8 @@ __global__ __launch_bounds__(512, 1) void halo256r_kernel(BlockConvArgs a) {
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
             f32x4& c = acc[i][jb + 2 * jj + (e >> 1)];
-            c[2 * (e & 1)] += __uint_as_float(q[e] << 16);
-            c[2 * (e & 1) + 1] += __uint_as_float(q[e] & 0xFFFF0000u);
+            c[2 * (e & 1)] += lo16<E>(q[e]);
+            c[2 * (e & 1) + 1] += hi16<E>(q[e]);
           }
         }
     };
@@ -419,8 +425,8 @@ __global__ __launch_bounds__(512, 1) void halo256r_kernel(BlockConvArgs a) {
             continue;
           }
           const int co = cw + i * 16 + (fg >> 1) * 8;
-          uint32_t q[4] = {h31_pk(acc[i][j][0], acc[i][j][1]), h31_pk(acc[i][j][2], acc[i][j][3]),
-                           h31_pk(acc[i][j + 1][0], acc[i][j + 1][1]), h31_pk(acc[i][j + 1][2], acc[i][j + 1][3])};
+          uint32_t q[4] = {h31_pk<E>(acc[i][j][0], acc[i][j][1]), h31_pk<E>(acc[i][j][2], acc[i][j][3]),
+                           h31_pk<E>(acc[i][j + 1][0], acc[i][j + 1][1]), h31_pk<E>(acc[i][j + 1][2], acc[i][j + 1][3])};
           if (a.relu)
 #pragma unroll
             for (int e = 0; e < 4; ++e) q[e] = h31_relu2(q[e]);
@@ -498,12 +504,12 @@ __global__ __launch_bounds__(512, 1) void halo256r_kernel(BlockConvArgs a) {
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
-template <int BC, bool POOL, bool X3, bool RES = false>
+template <int BC, bool POOL, bool X3, bool RES = false, typename E = u16>
 static int launch_halo256r_t(const BlockConvArgs& a, hipStream_t s) {
   using namespace h31;
   static bool attr = false;
   if (!attr) {
-    (void)hipFuncSetAttribute((const void*)halo256r_kernel<BC, POOL, X3, RES>,
+    (void)hipFuncSetAttribute((const void*)halo256r_kernel<BC, POOL, X3, RES, E>,
                               hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
     attr = true;
   }
@@ -511,7 +517,7 @@ static int launch_halo256r_t(const BlockConvArgs& a, hipStream_t s) {
   const int64_t tiles_p = (int64_t)a.N * (a.H / TH) * (a.W / TW);
   int64_t g = std::min<int64_t>(tiles_p * n_tc, 256);
   g = std::max<int64_t>(n_tc, g / n_tc * n_tc);
-  hipLaunchKernelGGL((halo256r_kernel<BC, POOL, X3, RES>), dim3((unsigned)g), dim3(512), SMEM, s, a);
+  hipLaunchKernelGGL((halo256r_kernel<BC, POOL, X3, RES, E>), dim3((unsigned)g), dim3(512), SMEM, s, a);
   SAD_CHECK_HIP(hipGetLastError());
   return SAD_OK;
 }
@@ -519,7 +525,8 @@ static int launch_halo256r_t(const BlockConvArgs& a, hipStream_t s) {
 // (a: the kernel's bf16 channel counts and strides, as launch_block_conv passes
 // them; x3: the split-bf16 layout, Cin / Cin1 / strides / wt_ld already doubled,
 // Cout and the bias logical)
-int launch_halo256r(const BlockConvArgs& a, hipStream_t s, bool x3) {
+int launch_halo256r(const BlockConvArgs& a, hipStream_t s, bool x3, bool h16) {
+  SAD_REQUIRE(!(x3 && h16), "variant 31: fp16 has no split form");
   SAD_REQUIRE(a.KH == 3 && a.KW == 3 && a.stride == 1 && a.pad == 1, "variant 31: 3x3, stride 1, pad 1");
   SAD_REQUIRE(!a.st_part, "variant 31: no fused statistics");
   SAD_REQUIRE(!a.res || (!x3 && !a.in1),
@@ -539,6 +546,19 @@ int launch_halo256r(const BlockConvArgs& a, hipStream_t s, bool x3) {
   SAD_REQUIRE((int64_t)(18 * a.W + 18) * a.in0_pstride * 2 < (1 << 30) &&
                   (!a.in1 || (int64_t)(16 * a.W1 + 16) * a.ss1 * a.in1_pstride * 2 < (1 << 30)),
               "variant 31: a patch's source offsets must fit the piece table's 30 bits");
+  if (h16) {  // bf16's instantiations, element type fp16
+    if (a.pool_out) {
+      SAD_REQUIRE(a.H == 16 && a.W == 16 && a.Cout % 256 == 0,
+                  "variant 31 fused average pool: a 16 x 16 tile must be one image, Cout % 256");
+      return a.res ? launch_halo256r_t<256, true, false, true, f16>(a, s)
+                   : launch_halo256r_t<256, true, false, false, f16>(a, s);
+    }
+    if (a.res)
+      return a.Cout % 256 == 0 ? launch_halo256r_t<256, false, false, true, f16>(a, s)
+                               : launch_halo256r_t<128, false, false, true, f16>(a, s);
+    return a.Cout % 256 == 0 ? launch_halo256r_t<256, false, false, false, f16>(a, s)
+                             : launch_halo256r_t<128, false, false, false, f16>(a, s);
+  }
   if (a.pool_out) {
     SAD_REQUIRE(a.H == 16 && a.W == 16 && a.Cout % 256 == 0,
                 "variant 31 fused average pool: a 16 x 16 tile must be one image, Cout % 256");

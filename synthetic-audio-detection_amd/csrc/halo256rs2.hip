@@ -96,7 +96,9 @@ __device__ __forceinline__ int h44_key(int x) { return (int)((h44::KEY >> (3 * x
 typedef unsigned int h44_v4 __attribute__((ext_vector_type(4)));
 typedef __bf16 h44_bf2 __attribute__((ext_vector_type(2)));
 typedef float h44_f2 __attribute__((ext_vector_type(2)));
+template <typename E = u16>
 __device__ __forceinline__ uint32_t h44_pk(float lo, float hi) {
+  if constexpr (is_f16_v<E>) return pk_f16(lo, hi);  // v_cvt_pk_f16_f32, saturating
   return __builtin_bit_cast(uint32_t, __builtin_convertvector((h44_f2){lo, hi}, h44_bf2));
 }
 __device__ __forceinline__ uint32_t h44_relu2(uint32_t x) {
@@ -105,8 +107,11 @@ __device__ __forceinline__ uint32_t h44_relu2(uint32_t x) {
   return r;
 }
 
-template <int BC, bool X3>
+// E = f16 (SAD_F16): fp16 tensors (the f16 MFMA, saturating fp16 stores)
+template <int BC, bool X3, typename E = u16>
 __global__ __launch_bounds__(512, 1) void halo256rs2_kernel(BlockConvArgs a) {
+  static_assert(!is_f16_v<E> || !X3, "fp16 has no split form");
+  f16_kernel_entry<E>();
   using namespace h44;
   constexpr int NCG = BC / 32, NPG = NW / NCG, TP = 16 / NPG;
   static_assert(NCG * NPG == NW, "wave split");
@@ -238,7 +243,7 @@ __global__ __launch_bounds__(512, 1) void halo256rs2_kernel(BlockConvArgs a) {
         for (int m = 0; m < NM; ++m)
 #pragma unroll
           for (int i = 0; i < TC; ++i)
-            mfma_chunk<u16>(__builtin_bit_cast(uint4, wcur[i][X3 ? m : h]), bf[j], acc[i][j]);
+            mfma_chunk<E>(__builtin_bit_cast(uint4, wcur[i][X3 ? m : h]), bf[j], acc[i][j]);
       __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);
 #pragma unroll
       for (int j = 0; j < TP - 4; ++j) {
@@ -292,8 +297,8 @@ __global__ __launch_bounds__(512, 1) void halo256rs2_kernel(BlockConvArgs a) {
         }
         // 16-B stores: v_permlane16_swap pairs fragment rows j, j + 1 (variant 31)
         const int co = cw + i * 16 + (fg >> 1) * 8;
-        uint32_t q[4] = {h44_pk(acc[i][j][0], acc[i][j][1]), h44_pk(acc[i][j][2], acc[i][j][3]),
-                         h44_pk(acc[i][j + 1][0], acc[i][j + 1][1]), h44_pk(acc[i][j + 1][2], acc[i][j + 1][3])};
+        uint32_t q[4] = {h44_pk<E>(acc[i][j][0], acc[i][j][1]), h44_pk<E>(acc[i][j][2], acc[i][j][3]),
+                         h44_pk<E>(acc[i][j + 1][0], acc[i][j + 1][1]), h44_pk<E>(acc[i][j + 1][2], acc[i][j + 1][3])};
         if (a.relu)
 #pragma unroll
           for (int e = 0; e < 4; ++e) q[e] = h44_relu2(q[e]);
@@ -364,12 +369,12 @@ __global__ __launch_bounds__(512, 1) void halo256rs2_kernel(BlockConvArgs a) {
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
-template <int BC, bool X3>
+template <int BC, bool X3, typename E = u16>
 static int launch_halo256rs2_t(const BlockConvArgs& a, hipStream_t s) {
   using namespace h44;
   static bool attr = false;
   if (!attr) {
-    SAD_CHECK_HIP(hipFuncSetAttribute((const void*)halo256rs2_kernel<BC, X3>,
+    SAD_CHECK_HIP(hipFuncSetAttribute((const void*)halo256rs2_kernel<BC, X3, E>,
                                       hipFuncAttributeMaxDynamicSharedMemorySize, SMEM));
     attr = true;
   }
@@ -377,7 +382,7 @@ static int launch_halo256rs2_t(const BlockConvArgs& a, hipStream_t s) {
   const int64_t tiles_p = (int64_t)a.N * (a.Ho / 16) * (a.Wo / 16);
   int64_t g = std::min<int64_t>(tiles_p * n_tc, 256);
   g = std::max<int64_t>(n_tc, g / n_tc * n_tc);
-  hipLaunchKernelGGL((halo256rs2_kernel<BC, X3>), dim3((unsigned)g), dim3(512), SMEM, s, a);
+  hipLaunchKernelGGL((halo256rs2_kernel<BC, X3, E>), dim3((unsigned)g), dim3(512), SMEM, s, a);
   SAD_CHECK_HIP(hipGetLastError());
   return SAD_OK;
 }
@@ -392,7 +397,8 @@ bool halo256rs2_ok(const BlockConvArgs& a) {
 // (a: the kernel's bf16 channel counts and strides, as launch_block_conv passes
 // them; x3: the split-bf16 layout, Cin / strides / wt_ld already doubled, Cout
 // and the bias logical)
-int launch_halo256rs2(const BlockConvArgs& a, hipStream_t s, bool x3) {
+int launch_halo256rs2(const BlockConvArgs& a, hipStream_t s, bool x3, bool h16) {
+  SAD_REQUIRE(!(x3 && h16), "variant 44: fp16 has no split form");
   SAD_REQUIRE(a.KH == 3 && a.KW == 3 && a.stride == 2 && a.pad == 1 && !a.in1 && !a.res && !a.st_part &&
                   !a.pool_out,
               "variant 44: 3x3/s2/p1, no shortcut / residual / pool / statistics");
@@ -405,6 +411,8 @@ int launch_halo256rs2(const BlockConvArgs& a, hipStream_t s, bool x3) {
   SAD_REQUIRE(a.M == (int64_t)a.N * a.Ho * a.Wo, "variant 44: M = N Ho Wo");
   SAD_REQUIRE(((int64_t)a.N * a.H * a.W - 1) * a.in0_pstride * 2 + 2 * a.Cin < (1ll << 31) - 65536,
               "variant 44: input passes the 32-bit buffer range");
+  if (h16)
+    return a.Cout % 256 == 0 ? launch_halo256rs2_t<256, false, f16>(a, s) : launch_halo256rs2_t<128, false, f16>(a, s);
   if (x3)
     return a.Cout % 256 == 0 ? launch_halo256rs2_t<256, true>(a, s) : launch_halo256rs2_t<128, true>(a, s);
   return a.Cout % 256 == 0 ? launch_halo256rs2_t<256, false>(a, s) : launch_halo256rs2_t<128, false>(a, s);

@@ -11,6 +11,10 @@ struct DT<u16> {
   static constexpr int EPC = 8;  // elements per 16-B chunk
 };
 template <>
+struct DT<f16> {
+  static constexpr int EPC = 8;
+};
+template <>
 struct DT<float> {
   static constexpr int EPC = 4;
 };
@@ -56,6 +60,11 @@ template <>
 __device__ __forceinline__ void mfma_chunk<u16>(const uint4& a, const uint4& b, f32x4& acc) {
   acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a),
                                                 __builtin_bit_cast(bf16x8, b), acc, 0, 0, 0);
+}
+template <>
+__device__ __forceinline__ void mfma_chunk<f16>(const uint4& a, const uint4& b, f32x4& acc) {
+  acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), acc, 0, 0,
+                                               0);
 }
 template <>
 __device__ __forceinline__ void mfma_chunk<float>(const uint4& a, const uint4& b, f32x4& acc) {

@@ -80,7 +80,7 @@ struct BlockConvArgs {
                          // resnet.hip); runs on the implicit-GEMM variants
 };
 
-// Fused layer1 BasicBlock (l1block.hip, variant 40): bf16 NHWC, 64 channels,
+// Fused layer1 BasicBlock (l1block.hip, variant 40): bf16 (or fp16: h16) NHWC, 64 channels,
 // pixel stride 64; out = relu(conv(relu(conv(x; w1) + b1); w2) + b2 + x)
 struct L1BlockArgs {
   const u16* x;          // [N, H, W, 64]
@@ -95,10 +95,11 @@ struct L1BlockArgs {
   int64_t x_bytes;       // set by launch_l1block
   int ablate;            // timing ablations (wrong results): 1 no patch DMA, 2 no intermediate stores, 4 no output stores
   uint64_t* stamps;      // diagnostic builds only (-DSAD_STAMPS): s_memtime per tile phase
+  int h16;               // every tensor is fp16 (SAD_F16) instead of bf16
 };
 int launch_l1block(const L1BlockArgs& a, hipStream_t s);
 int64_t block_conv_kernel_launches();  // kernels dispatched by launch_block_conv on this host thread so far (image-range launches each count)
-bool l1_fused();  // SAD_L1_FUSED (default 1): bf16 layer1 BasicBlocks on the fused kernel (ResNet-18 and the generic plan)
+bool l1_fused();  // SAD_L1_FUSED (default 1): bf16 / fp16 layer1 BasicBlocks on the fused kernel (ResNet-18 and the generic plan)
 
 struct StemArgs {
   const float* map;      // [B, mh, mw] standardised maps (bilinearly resized in-kernel), or
@@ -150,11 +151,14 @@ int upload(void** dst, const std::vector<V>& v) {
 // BN (eval) as a per-channel affine: scale = g / sqrt(var + 1e-5), shift = beta - mu * scale
 void fold_bn(const float* g, const float* beta, const float* mu, const float* var, int c,
              std::vector<double>& scale, std::vector<double>& shift);
-// fp32, bf16 (RNE) or split-bf16 (row_len: K per weight row, hi/lo interleaved per 32)
+// fp32, bf16 / fp16 (RNE) or split-bf16 (row_len: K per weight row, hi/lo interleaved per 32)
 int upload_typed(void** dst, const std::vector<double>& v, int dtype, int64_t row_len = 0);
 // timm conv1 + bn1 (5 arrays) -> the stem kernel's weight layout and bias, and
 // (w3_out) the per-channel fp32 weights of the 3-distinct-channel stem
 int fold_stem(const float* const* params, int dtype, void** w_out, float** b_out, float** w3_out);
+// fp16 plans: SAD_ERR_ARG (the message names the conv) for a folded weight past
+// +-65504 or a folded weight or bias that is not finite
+int check_f16_range(const std::vector<double>& w, const std::vector<float>& b, const std::string& name);
 // The stems' in-kernel resize is a plain bilinear sample: right for an upsample
 // only (a side above 512 would be point-sampled where the reference's
 // Resize((512,512)) applies its antialias filter).  SAD_ERR_ARG for such a map.
@@ -177,10 +181,10 @@ struct BasicBlock {
 // shortcut's columns (ds: the downsample's group over ds_cin channels; identity:
 // a cout x cout identity) whose shift joins the bias; *ld = elements per row.
 int fold_conv(const float* const* q, int cout, int cin, int k, int dtype, void** w, float** b, int* ld,
-              const float* const* ds = nullptr, int ds_cin = 0, bool identity = false);
+              const float* const* ds = nullptr, int ds_cin = 0, bool identity = false, const char* name = "conv");
 // q1 = conv1 + bn1, q2 = conv2 + bn2, qd = downsample + bn or null (identity shortcut)
 int fold_basic_block(const float* const* q1, const float* const* q2, const float* const* qd, int cin, int cout,
-                     int stride, int dtype, BasicBlock& out);
+                     int stride, int dtype, BasicBlock& out, const char* name = "block");
 void free_basic_block(BasicBlock& b);
 // The block's launches on n images: x [n, H, H, cin] -> y [n, H/stride, H/stride, cout]
 // (NHWC, plan dtype; tmp holds conv1's output).  pool_out (optional): conv2 also

@@ -120,8 +120,13 @@ __device__ __forceinline__ int l1b_key(int x) { return (int)((l1b::KEY >> (3 * x
 // AB: false = the production kernel, which holds no ablation code at all; true
 // = the timing-ablation form, which tests a.ablate at run time around the
 // patch DMA and the stores (launch_l1block picks it when ablate != 0).
-template <bool AB>
+// E = f16 (L1BlockArgs.h16, SAD_F16): fp16 tensors -- the f16 MFMA, saturating
+// v_cvt_pk_f16_f32 for the intermediate and the output, v_cvt_f32_f16 for the
+// identity's halves; the packed integer ReLU serves both formats.
+template <bool AB, typename E = u16>
 __device__ __forceinline__ void l1block_body(const L1BlockArgs& a) {
+  static_assert(!is_f16_v<E> || !AB, "fp16: the production form");
+  f16_kernel_entry<E>();
   using namespace l1b;
   extern __shared__ __attribute__((aligned(128))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63;
@@ -383,11 +388,11 @@ __device__ __forceinline__ void l1block_body(const L1BlockArgs& a) {
       if constexpr ((part & 1) == 0) {
         // (the mask, all ones or zero, commutes with the ReLU; applied first,
         // no VALU reads v_pk_max_i16's result right behind it: that costs an s_nop)
-        e1_qx = l1b_relu2(l1b_pk(acc[i][k][0], acc[i][k][1]) & e1_inm);
+        e1_qx = l1b_relu2(l1b_pk<E>(acc[i][k][0], acc[i][k][1]) & e1_inm);
       } else {
         l1b_v2 q;
         q.x = e1_qx;
-        q.y = l1b_relu2(l1b_pk(acc[i][k][2], acc[i][k][3]) & e1_inm);
+        q.y = l1b_relu2(l1b_pk<E>(acc[i][k][2], acc[i][k][3]) & e1_inm);
         if (!(ab & 2)) l1b_st<l1b_v2>(k < NA ? E1A[i] + k * IROW : E1L[i], q);
       }
     };
@@ -438,9 +443,9 @@ __device__ __forceinline__ void l1block_body(const L1BlockArgs& a) {
 #pragma unroll
           for (int i = 0; i < 2; ++i) {
             if (st == 0)
-              l1b_mfma_ac(pa[i], w1r[i][st], bf, b1v[i]);
+              l1b_mfma_ac<E>(pa[i], w1r[i][st], bf, b1v[i]);
             else
-              l1b_mfma_a(pa[i], w1r[i][st], bf);
+              l1b_mfma_a<E>(pa[i], w1r[i][st], bf);
           }
         }
         __builtin_amdgcn_sched_barrier(0);
@@ -453,8 +458,8 @@ __device__ __forceinline__ void l1block_body(const L1BlockArgs& a) {
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
           uint2 q;
-          q.x = l1b_relu2(l1b_pk(pa[i][0], pa[i][1])) & inm;
-          q.y = l1b_relu2(l1b_pk(pa[i][2], pa[i][3])) & inm;
+          q.x = l1b_relu2(l1b_pk<E>(pa[i][0], pa[i][1])) & inm;
+          q.y = l1b_relu2(l1b_pk<E>(pa[i][2], pa[i][3])) & inm;
           *(uint2*)(smem + pix + (i ? pos ^ 32 : pos)) = q;
         }
       };
@@ -475,9 +480,9 @@ __device__ __forceinline__ void l1block_body(const L1BlockArgs& a) {
 #pragma unroll
       for (int i = 0; i < 2; ++i) {
         if constexpr (s == 0)
-          l1b_mfma_ac(acc[i][k], w1r[i][s], bf, b1v[i]);
+          l1b_mfma_ac<E>(acc[i][k], w1r[i][s], bf, b1v[i]);
         else
-          l1b_mfma_a(acc[i][k], w1r[i][s], bf);
+          l1b_mfma_a<E>(acc[i][k], w1r[i][s], bf);
       }
       // fragment k-1 is complete: its epilogue parts go after units 2, 4, 6, 8
       // of fragment k (>= 6 MFMAs after its last one: the XDL -> VALU read
@@ -517,10 +522,10 @@ __device__ __forceinline__ void l1block_body(const L1BlockArgs& a) {
     };
     auto init2_add = [&](auto jc, auto ic) __attribute__((always_inline)) {
       constexpr int jj = decltype(jc)::value, i = decltype(ic)::value;
-      acc2[i][jj][0] = i2b[i][0] + __uint_as_float(i2r[i].x << 16);
-      acc2[i][jj][1] = i2b[i][1] + __uint_as_float(i2r[i].x & 0xFFFF0000u);
-      acc2[i][jj][2] = i2b[i][2] + __uint_as_float(i2r[i].y << 16);
-      acc2[i][jj][3] = i2b[i][3] + __uint_as_float(i2r[i].y & 0xFFFF0000u);
+      acc2[i][jj][0] = i2b[i][0] + lo16<E>(i2r[i].x);
+      acc2[i][jj][1] = i2b[i][1] + hi16<E>(i2r[i].x);
+      acc2[i][jj][2] = i2b[i][2] + lo16<E>(i2r[i].y);
+      acc2[i][jj][3] = i2b[i][3] + hi16<E>(i2r[i].y);
     };
     auto init2 = [&](auto jc, auto ic) __attribute__((always_inline)) {
       init2_rd(jc, ic);
@@ -549,11 +554,11 @@ __device__ __forceinline__ void l1block_body(const L1BlockArgs& a) {
     auto epi2 = [&](auto jc, auto pc) __attribute__((always_inline)) {
       constexpr int jj = decltype(jc)::value, part = decltype(pc)::value, i = part >> 1;
       if constexpr ((part & 1) == 0) {
-        e2_qx = l1b_relu2(l1b_pk(acc2[i][jj][0], acc2[i][jj][1]));
+        e2_qx = l1b_relu2(l1b_pk<E>(acc2[i][jj][0], acc2[i][jj][1]));
       } else {
         uint2 q;
         q.x = e2_qx;
-        q.y = l1b_relu2(l1b_pk(acc2[i][jj][2], acc2[i][jj][3]));
+        q.y = l1b_relu2(l1b_pk<E>(acc2[i][jj][2], acc2[i][jj][3]));
         if (!(ab & 4))
           __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(l1b_v2, q), ro,
                                                 OV + 32 * i, obase + jj * row_b, 0);
@@ -584,9 +589,9 @@ __device__ __forceinline__ void l1block_body(const L1BlockArgs& a) {
         constexpr int i = decltype(ic)::value;
         // the last K-steps' weights of channel tile 1 sit in VGPRs
         if constexpr (i == 1 && s >= NS - W2V)
-          l1b_mfma_v(acc2[i][jj], w2r[i][s], bf);
+          l1b_mfma_v<E>(acc2[i][jj], w2r[i][s], bf);
         else
-          l1b_mfma_a(acc2[i][jj], w2r[i][s], bf);
+          l1b_mfma_a<E>(acc2[i][jj], w2r[i][s], bf);
       });
       // fragment jj-1's epilogue parts after units 2, 4, 6, 8 of fragment jj,
       // fragment jj+1's accumulator init: its reads after units 5 and 7, the
@@ -638,6 +643,7 @@ __device__ __forceinline__ void l1block_body(const L1BlockArgs& a) {
 
 __global__ __launch_bounds__(256, 1) void l1block_kernel(L1BlockArgs a) { l1block_body<false>(a); }
 __global__ __launch_bounds__(256, 1) void l1block_ablate_kernel(L1BlockArgs a) { l1block_body<true>(a); }
+__global__ __launch_bounds__(256, 1) void l1block_f16_kernel(L1BlockArgs a) { l1block_body<false, f16>(a); }
 
 int launch_l1block(const L1BlockArgs& a_in, hipStream_t s) {
   using namespace l1b;
@@ -646,9 +652,11 @@ int launch_l1block(const L1BlockArgs& a_in, hipStream_t s) {
               "fused layer1 block: H, W multiples of 16");
   SAD_REQUIRE(a_in.w1_ld >= 576 && a_in.w2_ld >= 576 && a_in.w1_ld % 8 == 0 && a_in.w2_ld % 8 == 0,
               "fused layer1 block: weight rows of >= 576 bf16, 16-B aligned");
+  SAD_REQUIRE(!(a_in.h16 && a_in.ablate), "fused layer1 block: no timing ablations in fp16");
   if (a_in.N == 0) return SAD_OK;
   static bool attr = false;
   if (!attr) {
+    SAD_CHECK_HIP(hipFuncSetAttribute((const void*)l1block_f16_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM));
     SAD_CHECK_HIP(hipFuncSetAttribute((const void*)l1block_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM));
     SAD_CHECK_HIP(
         hipFuncSetAttribute((const void*)l1block_ablate_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM));
@@ -672,7 +680,9 @@ int launch_l1block(const L1BlockArgs& a_in, hipStream_t s) {
     SAD_CHECK_HIP(hipMemsetAsync(sbuf, 0, 2 * 8192 * 8, s));
     a.stamps = sbuf;
 #endif
-    if (a.ablate == 0)
+    if (a.h16)
+      hipLaunchKernelGGL(l1block_f16_kernel, dim3((unsigned)g), dim3(256), SMEM, s, a);
+    else if (a.ablate == 0)
       hipLaunchKernelGGL(l1block_kernel, dim3((unsigned)g), dim3(256), SMEM, s, a);
     else
       hipLaunchKernelGGL(l1block_ablate_kernel, dim3((unsigned)g), dim3(256), SMEM, s, a);

@@ -87,8 +87,12 @@ __device__ __forceinline__ int l2c_key(int x) { return (int)((l2c::KEY >> (3 * x
 // patch piece is one table read, 4 VALU and the DMA; a residual / downsample
 // piece is one lane constant plus a scalar; the fragment, store, residual and
 // bias addresses are lane constants formed once per launch.
-template <bool RES, bool DS, bool X3, bool ST, bool AB>
+// E = f16 (SAD_F16): fp16 tensors in the bf16 inference forms -- the f16 MFMA,
+// saturating v_cvt_pk_f16_f32 stores, v_cvt_f32_f16 for the residual's halves.
+template <bool RES, bool DS, bool X3, bool ST, bool AB, typename E = u16>
 __device__ __forceinline__ void l2conv_body(const BlockConvArgs& a) {
+  static_assert(!is_f16_v<E> || (!X3 && !ST && !AB), "fp16: the plain inference forms");
+  f16_kernel_entry<E>();
   static_assert(!(RES && DS) && !(X3 && DS), "one shortcut form");
   static_assert(!ST || (!RES && !DS && !X3), "statistics: the plain bf16 form");
   static_assert(!AB || (!X3 && !ST), "ablations: the bf16 forms");
@@ -371,9 +375,9 @@ __device__ __forceinline__ void l2conv_body(const BlockConvArgs& a) {
         auto mm = [&](auto ic, auto sc) __attribute__((always_inline)) {
           constexpr int i = decltype(ic)::value, ss = decltype(sc)::value;
           if constexpr (i == 1 && ss >= NS - WV)
-            l1b_mfma_v(acc[i][j], wr[i][ss], bf);
+            l1b_mfma_v<E>(acc[i][j], wr[i][ss], bf);
           else
-            l1b_mfma_a(acc[i][j], wr[i][ss], bf);
+            l1b_mfma_a<E>(acc[i][j], wr[i][ss], bf);
         };
         if constexpr (!X3) {
           mm(std::integral_constant<int, 0>{}, std::integral_constant<int, s>{});
@@ -438,8 +442,8 @@ __device__ __forceinline__ void l2conv_body(const BlockConvArgs& a) {
         constexpr int u = decltype(uc)::value, h = u / 16, j = u % 16;
         const l1b_v4 bf = bd[u % DQD];
         if constexpr (u + DQD < 32) bd[u % DQD] = rdd(std::integral_constant<int, u + DQD>{});
-        l1b_mfma_v(acc[0][j], wds[0][h], bf);
-        l1b_mfma_v(acc[1][j], wds[1][h], bf);
+        l1b_mfma_v<E>(acc[0][j], wds[0][h], bf);
+        l1b_mfma_v<E>(acc[1][j], wds[1][h], bf);
       });
     }
     // asm MFMA results read by compiler code: 12 wait states (8-pass XDL)
@@ -513,14 +517,14 @@ __device__ __forceinline__ void l2conv_body(const BlockConvArgs& a) {
           // residual of channels cw + 16 i + 4 fg .. +3 of pixels (j, fr), (j + 1, fr)
           const l1b_v2 r0 = l1b_ld<l1b_v2>(rbi + j * 4096);
           const l1b_v2 r1 = l1b_ld<l1b_v2>(rbi + (j + 1) * 4096);
-          v0[0] += __uint_as_float(r0.x << 16);
-          v0[1] += __uint_as_float(r0.x & 0xFFFF0000u);
-          v0[2] += __uint_as_float(r0.y << 16);
-          v0[3] += __uint_as_float(r0.y & 0xFFFF0000u);
-          v1[0] += __uint_as_float(r1.x << 16);
-          v1[1] += __uint_as_float(r1.x & 0xFFFF0000u);
-          v1[2] += __uint_as_float(r1.y << 16);
-          v1[3] += __uint_as_float(r1.y & 0xFFFF0000u);
+          v0[0] += lo16<E>(r0.x);
+          v0[1] += hi16<E>(r0.x);
+          v0[2] += lo16<E>(r0.y);
+          v0[3] += hi16<E>(r0.y);
+          v1[0] += lo16<E>(r1.x);
+          v1[1] += hi16<E>(r1.x);
+          v1[2] += lo16<E>(r1.y);
+          v1[3] += hi16<E>(r1.y);
         }
         if constexpr (ST) {
 #pragma unroll
@@ -531,7 +535,8 @@ __device__ __forceinline__ void l2conv_body(const BlockConvArgs& a) {
             st_q[i][e] = fmaf(v1[e], v1[e], st_q[i][e]);
           }
         }
-        uint32_t q[4] = {l1b_pk(v0[0], v0[1]), l1b_pk(v0[2], v0[3]), l1b_pk(v1[0], v1[1]), l1b_pk(v1[2], v1[3])};
+        uint32_t q[4] = {l1b_pk<E>(v0[0], v0[1]), l1b_pk<E>(v0[2], v0[3]), l1b_pk<E>(v1[0], v1[1]),
+                         l1b_pk<E>(v1[2], v1[3])};
         if constexpr (!ST)  // (the statistics form is the raw conv: launch_l2conv requires !relu)
 #pragma unroll
           for (int e = 0; e < 4; ++e) q[e] = l1b_relu2s(q[e], rl);
@@ -575,9 +580,9 @@ __device__ __forceinline__ void l2conv_body(const BlockConvArgs& a) {
 
 // the production kernels hold no ablation code; launch_l2conv picks the
 // ablation twin (the bf16 inference forms only) when a.ablate != 0
-template <bool RES, bool DS, bool X3 = false, bool ST = false>
+template <bool RES, bool DS, bool X3 = false, bool ST = false, typename E = u16>
 __global__ __launch_bounds__(256, 1) void l2conv_kernel(BlockConvArgs a) {
-  l2conv_body<RES, DS, X3, ST, false>(a);
+  l2conv_body<RES, DS, X3, ST, false, E>(a);
 }
 template <bool RES, bool DS>
 __global__ __launch_bounds__(256, 1) void l2conv_ablate_kernel(BlockConvArgs a) {
@@ -586,10 +591,11 @@ __global__ __launch_bounds__(256, 1) void l2conv_ablate_kernel(BlockConvArgs a) 
 
 // (x3: the split layout's bf16 channel counts / strides, as launch_block_conv
 // passes them: Cin 128 = 64 logical, Cout and the bias logical 64)
-int launch_l2conv(const BlockConvArgs& a, hipStream_t s, bool x3) {
+int launch_l2conv(const BlockConvArgs& a, hipStream_t s, bool x3, bool h16) {
   using namespace l2c;
   SAD_REQUIRE(a.KH == 3 && a.KW == 3 && a.stride == 1 && a.pad == 1 && !a.pool_out,
               "variant 41/42: 3x3/s1/p1, no pool");
+  SAD_REQUIRE(!h16 || (!x3 && !a.st_part && !a.ablate), "variant 41 in fp16: the plain inference forms");
   SAD_REQUIRE(!a.st_part || (!x3 && !a.in1 && !a.res && !a.relu && a.st_rows),
               "variant 41 statistics: the plain bf16 raw conv (no shortcut / residual / ReLU), st_rows set");
   if (x3) {
@@ -644,9 +650,13 @@ int launch_l2conv(const BlockConvArgs& a, hipStream_t s, bool x3) {
     hipLaunchKernelGGL(kern, dim3((unsigned)g), dim3(256), smem, s, b);
     return SAD_OK;
   };
-  static bool attr[7] = {};
+  static bool attr[10] = {};
   int rc;
-  if (a.st_part) {
+  if (h16) {
+    rc = a.res   ? go(l2conv_kernel<true, false, false, false, f16>, SMEM_RES + TAIL, attr[7])
+         : a.in1 ? go(l2conv_kernel<false, true, false, false, f16>, SMEM_RES + TAIL, attr[8])
+                 : go(l2conv_kernel<false, false, false, false, f16>, OFF_RES + TAIL, attr[9]);
+  } else if (a.st_part) {
     rc = go(l2conv_kernel<false, false, false, true>, OFF_RES + TAIL, attr[6]);
     if (rc == SAD_OK) *a.st_rows = (int)g;
   } else if (a.res) {

@@ -72,8 +72,11 @@ __device__ __forceinline__ int l2s_key(int x) { return (int)((l2s::KEY >> (3 * x
 // ST (the trainer's raw conv): also the fused BN statistics, fp32 sums of the
 // accumulators and their squares per channel, one row of a.st_part
 // ([rows][2][128]) per workgroup
-template <bool ST = false>
+// E = f16 (SAD_F16): fp16 tensors (the f16 MFMA, saturating fp16 stores)
+template <bool ST = false, typename E = u16>
 __global__ __launch_bounds__(256, 1) void l2s2conv_kernel(BlockConvArgs a) {
+  static_assert(!is_f16_v<E> || !ST, "the fused statistics are the bf16 trainer's");
+  f16_kernel_entry<E>();
   using namespace l2s;
   const int ab = a.ablate;  // timing ablations (wrong results): 32 no patch DMA in the loop, 8 no epilogue stores
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -233,8 +236,8 @@ __global__ __launch_bounds__(256, 1) void l2s2conv_kernel(BlockConvArgs a) {
           else
             issue_piece(u / PDIV, onext, 0);
         }
-        l1b_mfma_a(acc[0][j], wr[0][s], bf);
-        l1b_mfma_a(acc[1][j], wr[1][s], bf);
+        l1b_mfma_a<E>(acc[0][j], wr[0][s], bf);
+        l1b_mfma_a<E>(acc[1][j], wr[1][s], bf);
       });
       // asm MFMA results read by compiler code: 12 wait states (8-pass XDL)
       __builtin_amdgcn_sched_barrier(0);
@@ -259,7 +262,8 @@ __global__ __launch_bounds__(256, 1) void l2s2conv_kernel(BlockConvArgs a) {
               st_q[i][e] = fmaf(v1[e], v1[e], st_q[i][e]);
             }
           }
-          uint32_t q[4] = {l1b_pk(v0[0], v0[1]), l1b_pk(v0[2], v0[3]), l1b_pk(v1[0], v1[1]), l1b_pk(v1[2], v1[3])};
+          uint32_t q[4] = {l1b_pk<E>(v0[0], v0[1]), l1b_pk<E>(v0[2], v0[3]), l1b_pk<E>(v1[0], v1[1]),
+                           l1b_pk<E>(v1[2], v1[3])};
           if (a.relu)
 #pragma unroll
             for (int e = 0; e < 4; ++e) q[e] = l1b_relu2(q[e]);
@@ -306,7 +310,7 @@ __global__ __launch_bounds__(256, 1) void l2s2conv_kernel(BlockConvArgs a) {
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
-int launch_l2s2conv(const BlockConvArgs& a, hipStream_t s) {
+int launch_l2s2conv(const BlockConvArgs& a, hipStream_t s, bool h16) {
   using namespace l2s;
   SAD_REQUIRE(a.KH == 3 && a.KW == 3 && a.stride == 2 && a.pad == 1 && !a.in1 && !a.res && !a.pool_out,
               "variant 43: 3x3/s2/p1, no shortcut, residual or pool");
@@ -323,7 +327,16 @@ int launch_l2s2conv(const BlockConvArgs& a, hipStream_t s) {
   BlockConvArgs b = a;
   b.out_bytes = ((int64_t)a.N * a.Ho * a.Wo - 1) * a.out_pstride * 2 + 256;
   SAD_REQUIRE(b.out_bytes < (1ll << 31) - 65536, "variant 43: output passes the 32-bit buffer range");
-  if (a.st_part) {
+  if (h16) {
+    SAD_REQUIRE(!a.st_part, "variant 43: no fused statistics in fp16");
+    static bool attr = false;
+    if (!attr) {
+      SAD_CHECK_HIP(hipFuncSetAttribute((const void*)l2s2conv_kernel<false, f16>,
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, SMEM));
+      attr = true;
+    }
+    hipLaunchKernelGGL((l2s2conv_kernel<false, f16>), dim3((unsigned)g), dim3(256), SMEM, s, b);
+  } else if (a.st_part) {
     static bool attr = false;
     if (!attr) {
       SAD_CHECK_HIP(hipFuncSetAttribute((const void*)l2s2conv_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM));

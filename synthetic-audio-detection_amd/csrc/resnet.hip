@@ -42,12 +42,12 @@ struct Bottleneck {
   ConvW c1, c2, c3;  // c3 + the downsample's K columns
 };
 
-int fold_conv(const float* const* q, int cout, int cin, int k, int dtype, ConvW& out,
+int fold_conv(const float* const* q, int cout, int cin, int k, int dtype, ConvW& out, const std::string& name,
               const float* const* ds = nullptr, int ds_cin = 0) {
   out.cin = cin;
   out.cout = cout;
   out.k = k;
-  return sad::fold_conv(q, cout, cin, k, dtype, &out.w, &out.b, &out.ld, ds, ds_cin);
+  return sad::fold_conv(q, cout, cin, k, dtype, &out.w, &out.b, &out.ld, ds, ds_cin, false, name.c_str());
 }
 
 bool deep_x4() {
@@ -99,7 +99,7 @@ extern "C" int sad_resnet_plan_create(const float* const* params, int32_t n_para
                                       sad_resnet_plan** out) {
   SAD_REQUIRE(params && layers && out, "null args");
   SAD_REQUIRE(block == SAD_BASIC_BLOCK || block == SAD_BOTTLENECK, "block must be SAD_BASIC_BLOCK or SAD_BOTTLENECK");
-  SAD_REQUIRE(dtype == SAD_F32 || dtype == SAD_BF16 || dtype == SAD_BF16X3, "dtype");
+  SAD_REQUIRE(dtype == SAD_F32 || dtype == SAD_BF16 || dtype == SAD_BF16X3 || dtype == SAD_F16, "dtype");
   SAD_REQUIRE(map_h > 0 && map_w > 0, "map shape");
   if (int rc = check_map_upsamples(map_h, map_w)) return rc;
   const int exp = block == SAD_BOTTLENECK ? 4 : 1;
@@ -140,15 +140,16 @@ extern "C" int sad_resnet_plan_create(const float* const* params, int32_t n_para
       const float* const* q3 = block == SAD_BOTTLENECK ? params + 5 * gi++ : nullptr;
       const float* const* qd = has_ds ? params + 5 * gi++ : nullptr;
       const int Ho = H / stride;
+      const std::string name = "layer" + std::to_string(li + 1) + "." + std::to_string(b);
       if (block == SAD_BASIC_BLOCK) {
         p->basic.emplace_back();
-        rc = fold_basic_block(q1, q2, qd, inp, cout, stride, dtype, p->basic.back());
+        rc = fold_basic_block(q1, q2, qd, inp, cout, stride, dtype, p->basic.back(), name.c_str());
       } else {
         p->blocks.push_back(Bottleneck{inp, planes[li], cout, stride, has_ds, {}, {}, {}});
         Bottleneck& blk = p->blocks.back();
-        rc = fold_conv(q1, blk.width, inp, 1, dtype, blk.c1);
-        if (!rc) rc = fold_conv(q2, blk.width, blk.width, 3, dtype, blk.c2);
-        if (!rc) rc = fold_conv(q3, cout, blk.width, 1, dtype, blk.c3, qd, inp);
+        rc = fold_conv(q1, blk.width, inp, 1, dtype, blk.c1, name + ".conv1");
+        if (!rc) rc = fold_conv(q2, blk.width, blk.width, 3, dtype, blk.c2, name + ".conv2");
+        if (!rc) rc = fold_conv(q3, cout, blk.width, 1, dtype, blk.c3, name + (qd ? ".conv3 + downsample" : ".conv3"), qd, inp);
         p->max_elems = std::max<int64_t>(p->max_elems, (int64_t)H * H * blk.width);
       }
       if (rc) {
@@ -171,7 +172,7 @@ extern "C" int sad_resnet_num_features(const sad_resnet_plan* p, int32_t* n) {
 }
 
 static size_t rn_act_bytes(const sad_resnet_plan* p, int64_t mb) {
-  const size_t es = p->dtype == SAD_BF16 ? 2 : 4;
+  const size_t es = dtype_bytes(p->dtype);
   return ((size_t)mb * p->max_elems * es + 255) & ~(size_t)255;
 }
 
@@ -215,7 +216,8 @@ static int rn_block_conv(const sad_resnet_plan* p, const ConvW& c, const void* x
   a.relu = 1;
   a.M = n * Ho * Ho;
   a.x4 = p->x4;
-  return launch_block_conv(a, p->dtype, s);
+  // (inside a sad_profile_* bracket the launch is recorded under its variant id)
+  return timed_block_conv(a, p->dtype, s, 2.0 * a.M * a.Cout * ((double)c.k * c.k * c.cin + (sc ? sc_cin : 0)));
 }
 
 static int rn_chunk(const sad_resnet_plan* p, const float* map, const float* img, int64_t n, float* feats, char* ws,
@@ -231,7 +233,7 @@ static int rn_chunk(const sad_resnet_plan* p, const float* map, const float* img
   if ((rc = launch_stem(st, p->dtype, s))) return rc;
   int H = 128, C = 64;
   for (const BasicBlock& b : p->basic) {
-    if ((rc = run_basic_block(b, p->dtype, X, T1, Y, n, H, s))) return rc;
+    if ((rc = run_basic_block(b, p->dtype, X, T1, Y, n, H, s, nullptr, nullptr, true))) return rc;
     std::swap(X, Y);
     H /= b.stride;
     C = b.cout;

@@ -12,37 +12,80 @@ namespace sad {
 
 typedef unsigned int l1b_v4 __attribute__((ext_vector_type(4)));
 typedef unsigned int l1b_v2 __attribute__((ext_vector_type(2)));
+// E: the element type (u16 = bf16, f16 = fp16, SAD_F16): the MFMA's type.
 // acc (VGPR) [+]= w (AGPR) . b (VGPR).  hipcc places MFMA A/B operands only
 // in VGPRs, and the 288 weight registers of both convs do not fit there next
 // to the accumulators: the weights live in AGPRs, the MFMA is inline asm.
+template <typename E = u16>
 __device__ __forceinline__ void l1b_mfma_a0(f32x4& acc, const l1b_v4& w, const uint4& b) {
-  asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, 0" : "=&v"(acc) : "a"(w), "v"(__builtin_bit_cast(l1b_v4, b)));
+  if constexpr (is_f16_v<E>) {
+    asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, 0" : "=&v"(acc) : "a"(w), "v"(__builtin_bit_cast(l1b_v4, b)));
+  } else {
+    asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, 0" : "=&v"(acc) : "a"(w), "v"(__builtin_bit_cast(l1b_v4, b)));
+  }
 }
+template <typename E = u16>
 __device__ __forceinline__ void l1b_mfma_a(f32x4& acc, const l1b_v4& w, const uint4& b) {
-  asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+v"(acc) : "a"(w), "v"(__builtin_bit_cast(l1b_v4, b)));
+  if constexpr (is_f16_v<E>) {
+    asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+v"(acc) : "a"(w), "v"(__builtin_bit_cast(l1b_v4, b)));
+  } else {
+    asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+v"(acc) : "a"(w), "v"(__builtin_bit_cast(l1b_v4, b)));
+  }
 }
 // acc = c + w . b (the first K-step: C = the bias)
+template <typename E = u16>
 __device__ __forceinline__ void l1b_mfma_ac(f32x4& acc, const l1b_v4& w, const uint4& b, const f32x4& c) {
-  asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %3"
-               : "=&v"(acc)
-               : "a"(w), "v"(__builtin_bit_cast(l1b_v4, b)), "v"(c));
+  if constexpr (is_f16_v<E>) {
+    asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %3"
+                 : "=&v"(acc)
+                 : "a"(w), "v"(__builtin_bit_cast(l1b_v4, b)), "v"(c));
+  } else {
+    asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %3"
+                 : "=&v"(acc)
+                 : "a"(w), "v"(__builtin_bit_cast(l1b_v4, b)), "v"(c));
+  }
 }
 // the same with the weights in VGPRs (the AGPR file holds 256 of the 288)
+template <typename E = u16>
 __device__ __forceinline__ void l1b_mfma_v0(f32x4& acc, const l1b_v4& w, const uint4& b) {
-  asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, 0" : "=&v"(acc) : "v"(w), "v"(__builtin_bit_cast(l1b_v4, b)));
+  if constexpr (is_f16_v<E>) {
+    asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, 0" : "=&v"(acc) : "v"(w), "v"(__builtin_bit_cast(l1b_v4, b)));
+  } else {
+    asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, 0" : "=&v"(acc) : "v"(w), "v"(__builtin_bit_cast(l1b_v4, b)));
+  }
 }
+template <typename E = u16>
 __device__ __forceinline__ void l1b_mfma_v(f32x4& acc, const l1b_v4& w, const uint4& b) {
-  asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+v"(acc) : "v"(w), "v"(__builtin_bit_cast(l1b_v4, b)));
+  if constexpr (is_f16_v<E>) {
+    asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+v"(acc) : "v"(w), "v"(__builtin_bit_cast(l1b_v4, b)));
+  } else {
+    asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+v"(acc) : "v"(w), "v"(__builtin_bit_cast(l1b_v4, b)));
+  }
 }
 // the same with the fragment as a native vector (HIP's uint4 is a struct)
+template <typename E = u16>
 __device__ __forceinline__ void l1b_mfma_a(f32x4& acc, const l1b_v4& w, const l1b_v4& b) {
-  asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+v"(acc) : "a"(w), "v"(b));
+  if constexpr (is_f16_v<E>) {
+    asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+v"(acc) : "a"(w), "v"(b));
+  } else {
+    asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+v"(acc) : "a"(w), "v"(b));
+  }
 }
+template <typename E = u16>
 __device__ __forceinline__ void l1b_mfma_ac(f32x4& acc, const l1b_v4& w, const l1b_v4& b, const f32x4& c) {
-  asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %3" : "=&v"(acc) : "a"(w), "v"(b), "v"(c));
+  if constexpr (is_f16_v<E>) {
+    asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %3" : "=&v"(acc) : "a"(w), "v"(b), "v"(c));
+  } else {
+    asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %3" : "=&v"(acc) : "a"(w), "v"(b), "v"(c));
+  }
 }
+template <typename E = u16>
 __device__ __forceinline__ void l1b_mfma_v(f32x4& acc, const l1b_v4& w, const l1b_v4& b) {
-  asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+v"(acc) : "v"(w), "v"(b));
+  if constexpr (is_f16_v<E>) {
+    asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+v"(acc) : "v"(w), "v"(b));
+  } else {
+    asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+v"(acc) : "v"(w), "v"(b));
+  }
 }
 // two floats -> packed bf16 pair (RNE), one v_cvt_pk_bf16_f32
 typedef __bf16 l1b_bf2 __attribute__((ext_vector_type(2)));
@@ -54,7 +97,8 @@ __device__ __forceinline__ float l1b_relu(float x) {
   return r;
 }
 // ReLU of a packed bf16 pair: as int16, negative bf16 values (and -0) are
-// negative, so max(x, 0) per half is relu (= relu before the rounding)
+// negative, so max(x, 0) per half is relu (= relu before the rounding); fp16
+// has the same sign-magnitude order, so the same instruction serves it
 __device__ __forceinline__ uint32_t l1b_relu2(uint32_t x) {
   uint32_t r;
   asm("v_pk_max_i16 %0, %1, 0" : "=v"(r) : "v"(x));
@@ -67,7 +111,9 @@ __device__ __forceinline__ uint32_t l1b_relu2s(uint32_t x, int floor2) {
   asm("v_pk_max_i16 %0, %1, %2" : "=v"(r) : "v"(x), "s"(floor2));
   return r;
 }
+template <typename E = u16>
 __device__ __forceinline__ uint32_t l1b_pk(float lo, float hi) {
+  if constexpr (is_f16_v<E>) return pk_f16(lo, hi);  // v_cvt_pk_f16_f32, saturating
   return __builtin_bit_cast(uint32_t, __builtin_convertvector((l1b_f2){lo, hi}, l1b_bf2));
 }
 

@@ -67,7 +67,9 @@ __device__ __forceinline__ float ld1(const T* p) {
 }
 template <typename T>
 __device__ __forceinline__ void st1(T* p, float v) {
-  if constexpr (sizeof(T) == 2)
+  if constexpr (is_f16_v<T>)
+    *(u16*)p = to16<f16>(v);
+  else if constexpr (sizeof(T) == 2)
     *(u16*)p = f2bf(v);
   else
     *p = v;
@@ -203,6 +205,7 @@ __global__ void stem_im2col_kernel(const T* __restrict__ img, int ih, int iw, in
 template <typename T>
 __global__ void pack_weight_kernel(const float* __restrict__ w, int cout, int cin, int k, int mode,
                                    T* __restrict__ out, int64_t total) {
+  f16_kernel_entry<T>();
   const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= total) return;
   const int kk = k * k;
@@ -713,13 +716,16 @@ extern "C" int sad_crop_resize_run(const float* map, int64_t n, int32_t h, int32
 extern "C" int sad_pack_conv_weight_run(const float* w, int32_t cout, int32_t cin, int32_t k, int32_t mode,
                                         int32_t dtype, void* out, void* stream) {
   SAD_REQUIRE(w && out && cout > 0 && cin > 0 && k > 0 && mode >= 0 && mode <= 4, "bad args");
-  SAD_REQUIRE(dtype == SAD_F32 || dtype == SAD_BF16, "dtype");
+  SAD_REQUIRE(dtype == SAD_F32 || dtype == SAD_BF16 || dtype == SAD_F16, "dtype");
   SAD_REQUIRE(mode != 2 || k * k <= 64, "stem pack needs k*k <= 64");
   SAD_REQUIRE(mode != 4 || k <= 8, "8x8-grid stem pack needs k <= 8");
   const int64_t total = mode == 2 || mode == 4 ? (int64_t)cout * 64 : (int64_t)cout * cin * k * k;
   if (dtype == SAD_BF16)
     hipLaunchKernelGGL(pack_weight_kernel<u16>, dim3(nblk(total)), dim3(256), 0, (hipStream_t)stream, w, cout, cin, k,
                        mode, (u16*)out, total);
+  else if (dtype == SAD_F16)
+    hipLaunchKernelGGL(pack_weight_kernel<f16>, dim3(nblk(total)), dim3(256), 0, (hipStream_t)stream, w, cout, cin, k,
+                       mode, (f16*)out, total);
   else
     hipLaunchKernelGGL(pack_weight_kernel<float>, dim3(nblk(total)), dim3(256), 0, (hipStream_t)stream, w, cout, cin,
                        k, mode, (float*)out, total);
@@ -1125,6 +1131,7 @@ extern "C" int sad_cast_run(const void* src, int32_t src_dtype, void* dst, int32
 extern "C" int sad_avgpool_run(const void* x, int64_t B, int32_t hw, int32_t C, int32_t dtype, float* out,
                                void* stream) {
   SAD_REQUIRE(x && out && B >= 0 && hw > 0 && C % 64 == 0, "bad args (C must be a multiple of 64)");
+  SAD_REQUIRE(dtype == SAD_F32 || dtype == SAD_BF16 || dtype == SAD_BF16X3 || dtype == SAD_F16, "dtype");
   return launch_avgpool(x, B, hw, C, out, dtype, (hipStream_t)stream);
 }
 

@@ -24,8 +24,9 @@ Differences (documented in DESIGN.md):
   * ``pretrained=True`` ImageNet weights (:35) need a network download; a
     checkpoint missing backbone keys is an error instead of being filled from
     them;
-  * extra, non-breaking flags: ``--precision {fp32,bf16}`` (default fp32 = the
-    reference's arithmetic; bf16 = throughput mode), ``--batch-size``
+  * extra, non-breaking flags: ``--precision {fp32,bf16x3,bf16,fp16}`` (default
+    fp32 = the reference's arithmetic; bf16 = throughput mode; fp16 = the same
+    kernels with 11 significant bits instead of 8), ``--batch-size``
     (default 128, the reference's mini-batch at :284) and ``--model-name``
     (default resnet18, the reference's hard-coded backbone; resnet34/50/101/152
     run on the generic ResNet plan).
@@ -362,7 +363,7 @@ def run_windows(model: ModularMultiHeadClassifier, chunks, sr: int, spec_cfg: Sp
 
 
 # 5. Main Inference Logic -------------------------------------------------------
-def main(argv=None):
+def build_parser() -> argparse.ArgumentParser:
     parser = argparse.ArgumentParser(
         description='Multi-head inference with overlapping windows using metadata from the merged model.')
     parser.add_argument('--merged-model', type=str, required=True, help='Path to merged .pth')
@@ -372,13 +373,18 @@ def main(argv=None):
     parser.add_argument('--confidence-threshold', type=float, default=0.45, help='Confidence threshold for segments.')
     parser.add_argument('--smooth', action='store_true', help='Apply smoothing across windows.')
     parser.add_argument('--output-json', type=str, default='results.json')
-    parser.add_argument('--precision', choices=['fp32', 'bf16x3', 'bf16'], default='fp32',
+    parser.add_argument('--precision', choices=['fp32', 'bf16x3', 'bf16', 'fp16'], default='fp32',
                         help='device arithmetic: fp32 (f32 MFMA), bf16x3 (split-bf16: logits within 1e-3 of fp32 '
-                             'at ~3x the fp32 speed) or bf16 (throughput; not logit-exact)')
+                             'at ~3x the fp32 speed), bf16 (throughput; not logit-exact) or fp16 (bf16\'s kernels '
+                             'with fp16 operands: about 8x finer rounding, values saturate at 65504)')
     parser.add_argument('--batch-size', type=int, default=128, help='windows per device launch')
     parser.add_argument('--model-name', default='resnet18', choices=list(_weights.ARCHS),
                         help='backbone of the merged sub-models (the reference hard-codes resnet18, :77,246)')
-    args = parser.parse_args(argv)
+    return parser
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
 
     seed = 9
     random.seed(seed)

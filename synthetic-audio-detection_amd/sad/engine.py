@@ -153,6 +153,19 @@ def _dtype_code(dtype: str) -> int:
     return _lib.DTYPES[dtype]
 
 
+def _tensor_dtype(dtype: str) -> torch.dtype:
+    """torch dtype of a plan's activations (bf16x3: bf16 pairs in the split layout)."""
+    return {'fp32': torch.float32, 'fp16': torch.float16}.get(dtype, torch.bfloat16)
+
+
+def _code_of(t: torch.Tensor) -> int:
+    """libsad dtype of an operator wrapper's tensors: fp32, bf16 or fp16."""
+    codes = {torch.float32: _lib.SAD_F32, torch.bfloat16: _lib.SAD_BF16, torch.float16: _lib.SAD_F16}
+    if t.dtype not in codes:
+        raise ValueError(f'tensors must be float32, bfloat16 or float16 (got {t.dtype})')
+    return codes[t.dtype]
+
+
 def to_split(x: torch.Tensor) -> torch.Tensor:
     """fp32 [..., C] -> the split-bf16 layout [..., 2C] bf16 of dtype 'bf16x3':
     per group of 32 channels [hi(32) | lo(32)], hi = bf16(x), lo = bf16(x - hi)."""
@@ -195,7 +208,7 @@ class Backbone:
         self.device = _dev(device)
         self.dtype = dtype
         self._dt = _dtype_code(dtype)
-        self.tdtype = torch.float32 if dtype == 'fp32' else torch.bfloat16
+        self.tdtype = _tensor_dtype(dtype)
         self.micro_batch = micro_batch
         arrays = _backbone_arrays(base_sd, backbone_param_shapes())
         self._plan = _lib.P()
@@ -258,7 +271,8 @@ class Backbone:
     def trunk(self, x: torch.Tensor, kind: str = 'maps') -> torch.Tensor:
         """Stem, layer1, layer2 and layer3 on maps [B,128,251] or images
         [B,512,512] -> layer3's output NHWC [B,32,32,256] in the plan's
-        activation layout (bf16x3: the split layout, 512 bf16 per pixel)."""
+        activation layout (fp16: torch.float16; bf16x3: the split layout, 512
+        bf16 per pixel)."""
         mp, ip = self._input(x, kind)
         B = x.shape[0]
         l3 = torch.empty(B, 32, 32, _act_channels(self.dtype, 256), device=self.device, dtype=self.tdtype)
@@ -609,12 +623,12 @@ class Engine:
 def conv2d(x: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, stride: int = 1, pad: int = 0,
            res: torch.Tensor | None = None, relu: bool = True, variant: int = 0,
            out: torch.Tensor | None = None) -> torch.Tensor:
-    """NHWC conv on the libsad implicit-GEMM kernel.  x [N,H,W,Cin] bf16|fp32,
+    """NHWC conv on the libsad implicit-GEMM kernel.  x [N,H,W,Cin] bf16|fp16|fp32,
     w [Cout,k,k,Cin] same dtype, bias [Cout] fp32, res [N,Ho,Wo,Cout] or None."""
     N, H, W, Cin = x.shape
     Cout, k = w.shape[0], w.shape[1]
     Ho, Wo = (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
-    dt = _lib.SAD_BF16 if x.dtype == torch.bfloat16 else _lib.SAD_F32
+    dt = _code_of(x)
     if out is None:
         out = torch.empty(N, Ho, Wo, Cout, device=x.device, dtype=x.dtype)
     with torch.cuda.device(x.device):
@@ -632,12 +646,13 @@ def block_conv(x: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, stride: int
     four=True (with split): the four-product form of the deep Bottleneck plans.
     x [N,H,W,Cin], sc [N,H1,W1,Cin1] or None, w [Cout, wt_ld] with the k*k*Cin
     conv taps first and the shortcut's Cin1 columns next (extra columns are
-    ignored), bias [Cout] fp32, res [N,Ho,Wo,Cout] (epilogue identity shortcut)."""
+    ignored), bias [Cout] fp32, res [N,Ho,Wo,Cout] (epilogue identity shortcut).
+    The tensors' dtype picks the mode: float32, bfloat16 or float16 ('fp16')."""
     N, H, W, Cin = x.shape
     Cout = w.shape[0]
     Cin1 = sc.shape[3] if sc is not None else 0
     Ho, Wo = (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
-    dt = _lib.SAD_BF16 if x.dtype == torch.bfloat16 else _lib.SAD_F32
+    dt = _code_of(x)
     if split:  # x, sc, res, out, w in the split-bf16 layout; channel counts are logical
         dt = _lib.SAD_BF16X3
         Cin, Cin1, wt_ld = Cin // 2, Cin1 // 2, w.stride(0) // 2
@@ -652,4 +667,24 @@ def block_conv(x: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, stride: int
                   _lib.ptr(w), wt_ld, _lib.ptr(bias), _lib.ptr(res), _lib.ptr(out), Cout, k, stride, pad,
                   int(relu), dt, variant | (_lib.SAD_CONV_FOUR_PRODUCTS if four else 0),
                   _lib.stream_handle(x.device))
+    return out
+
+
+def l1_block(x: torch.Tensor, w1: torch.Tensor, b1: torch.Tensor, w2: torch.Tensor, b2: torch.Tensor,
+             out: torch.Tensor | None = None) -> torch.Tensor:
+    """One whole layer1 BasicBlock as the fused kernel (sad_l1_block_run, variant
+    40): out = relu(conv3x3(relu(conv3x3(x; w1) + b1); w2) + b2 + x).  x NHWC
+    [N,H,W,64] bfloat16 or float16 (H, W multiples of 16); w1, w2 [64, >= 576]
+    of x's dtype, k = tap * 64 + ci; b1, b2 [64] fp32."""
+    if x.dtype not in (torch.bfloat16, torch.float16):
+        raise ValueError(f'the fused layer1 block runs in bfloat16 or float16 (got {x.dtype})')
+    assert w1.dtype == x.dtype and w2.dtype == x.dtype and x.is_contiguous() and x.shape[3] == 64
+    assert w1.stride(1) == 1 and w2.stride(1) == 1
+    N, H, W, _ = x.shape
+    if out is None:
+        out = torch.empty_like(x)
+    flags = _lib.SAD_L1_BLOCK_F16 if x.dtype == torch.float16 else 0
+    with torch.cuda.device(x.device):
+        _lib.call('sad_l1_block_run', _lib.ptr(x), N, H, W, _lib.ptr(w1), w1.stride(0), _lib.ptr(b1), _lib.ptr(w2),
+                  w2.stride(0), _lib.ptr(b2), _lib.ptr(out), flags, _lib.stream_handle(x.device))
     return out

@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Per-layer error budget of the bf16 plan (CPU emulation).
+"""Per-layer error budget of the bf16 plan, or with --round fp16 of the fp16
+plan (CPU emulation).
 
 Emulates the device plan's arithmetic on the CPU for ResNet-18 (BN folded into
 each conv in float64, conv2 + shortcut as one sum, fp32 accumulation, fused
@@ -15,8 +16,13 @@ emulation, over the 16 reference-fixture segments and model n6 (the bench's
 activations only, then one conv in bf16 with the rest fp32, and the cumulative
 tails (bf16 from conv i on).  The conclusion goes to DESIGN.md section 3b.
 
-Test infrastructure only (imports oracle/).  python tools/error_budget.py
+--round {bf16,fp16} picks the 16-bit format every switch rounds to (default
+bf16); --table prints only the summary table of both formats (all convs /
+weights only / activations only: README and DESIGN.md 3b quote it).
+
+Test infrastructure only (imports oracle/).  python tools/error_budget.py [--round fp16 | --table]
 """
+import argparse
 import os
 import sys
 
@@ -28,8 +34,11 @@ import torch  # noqa: E402
 import torch.nn.functional as F  # noqa: E402
 
 
+ROUND = torch.bfloat16  # the 16-bit format of the emulated plan (--round)
+
+
 def _bf(x):
-    return x.to(torch.bfloat16).float()
+    return x.to(ROUND).float()
 
 
 def fold(conv, bn):
@@ -82,7 +91,14 @@ def merged(model, feat):
     return torch.cat([torch.cat(syn, 1), torch.cat(real, 1).mean(1, keepdim=True)], 1)
 
 
-def main():
+def main(argv=None):
+    global ROUND
+    ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
+    ap.add_argument('--round', choices=['bf16', 'fp16'], default='bf16', help='the 16-bit format the switches round to')
+    ap.add_argument('--table', action='store_true', help='only the summary table, for both formats')
+    args = ap.parse_args(argv)
+    ROUND = {'bf16': torch.bfloat16, 'fp16': torch.float16}[args.round]
+    T = args.round
     from make_golden_models16 import segments16
     from oracle import frontend as ofe
     from oracle import resnet as ores
@@ -108,17 +124,26 @@ def main():
             print(f'{tag:34s} max|dlogit| {d:.3e}', flush=True)
             return d
 
-        row('all bf16 (throughput mode)', allset, allset)
-        row('weights bf16, activations fp32', allset, set(), img_bf=False)
-        row('activations bf16, weights fp32', set(), allset)
-        row('stem image band bf16 only', set(), set(), img_bf=True)
+        if args.table:
+            print('| rounding (max|dlogit| vs all-fp32) | all convs (W + X + image band) | weights only | '
+                  'activations only |\n|---|---|---|---|')
+            for name, dt in (('bf16', torch.bfloat16), ('fp16', torch.float16)):
+                ROUND = dt
+                d = [(merged(model, features(base, img, w, x, ib)) - ref).abs().max().item()
+                     for w, x, ib in ((allset, allset, True), (allset, set(), False), (set(), allset, True))]
+                print(f'| {name} | {d[0]:.2e} | {d[1]:.2e} | {d[2]:.2e} |')
+            return
+        row(f'all {T} (throughput mode)', allset, allset)
+        row(f'weights {T}, activations fp32', allset, set(), img_bf=False)
+        row(f'activations {T}, weights fp32', set(), allset)
+        row(f'stem image band {T} only', set(), set(), img_bf=True)
         for n in names:
-            row(f'only {n} bf16 (W+X)', {n}, {n}, img_bf=(n == 'stem'))
+            row(f'only {n} {T} (W+X)', {n}, {n}, img_bf=(n == 'stem'))
         for n in names:
-            row(f'only {n} weights bf16', {n}, set(), img_bf=False)
+            row(f'only {n} weights {T}', {n}, set(), img_bf=False)
         for i, n in enumerate(names):
             tail = set(names[i:])
-            row(f'bf16 from {n} on', tail, tail, img_bf=(i == 0))
+            row(f'{T} from {n} on', tail, tail, img_bf=(i == 0))
 
 
 if __name__ == '__main__':
