@@ -21,7 +21,8 @@
  *     exception: the experimental fused front end's counters, see
  *     sad_frontend_run);
  *   - *_run calls are asynchronous on the given hipStream_t (passed as void*),
- *     never allocate, never synchronise (graph-capturable);
+ *     never allocate, never synchronise (graph-capturable; one exception: the
+ *     FIRST sad_heads_grad_run on a plan builds its transposed weights);
  *   - distinct plans / streams may be used from different threads;
  *   - cross-stream hand-offs need only the usual event: an output written on
  *     one stream (a libsad call, or a collective on the NCCL/RCCL stream) may
@@ -352,6 +353,20 @@ int sad_backbone_run_debug(const sad_backbone_plan* plan, const float* map, int6
                            float* feats, void* layer4_out, void* workspace, size_t ws_bytes,
                            void* stream);
 
+/* One chunk with the layer4 activation kept (evidence maps, below): exactly one
+ * of map [B, map_h, map_w] and img [B, 512, 512] non-null; B <= the micro-batch
+ * the workspace was sized for (sad_backbone_workspace_size(B) bytes at least;
+ * SAD_ERR_NOMEM otherwise).  feats [B, 512] fp32; l4_out: caller-owned
+ * [B, 16, 16, 512] in the plan's activation layout (SAD_BF16 / SAD_F16: 2 B per
+ * value; SAD_F32: 4 B; SAD_BF16X3: 1024 bf16 per pixel, [hi 32 | lo 32] per 32
+ * channels).  It runs the un-pooled path of sad_backbone_run_debug.
+ * NOTE: this entry pools the STORED, rounded activation, while
+ * sad_backbone_run fuses the pool into the last conv (fp32 accumulators).  Its
+ * features can therefore differ from the ordinary run's by the activation
+ * rounding; they are exactly the mean of l4_out. */
+int sad_backbone_run_keep(const sad_backbone_plan* plan, const float* map, const float* img, int64_t B,
+                          float* feats, void* l4_out, void* workspace, size_t ws_bytes, void* stream);
+
 /* Shared-trunk ensembles: the ResNet-18 plan split after layer3.  Reference
  * training only ever changes layer4 and the head, so sub-models trained on one
  * frozen trunk differ in layer4 alone: the trunk (stem, layer1-3; 13.83 of the
@@ -434,6 +449,15 @@ int sad_resnet_run_img3(const sad_resnet_plan* plan, const float* img3, int64_t 
 int sad_resnet_stem_run(const sad_resnet_plan* plan, const float* map, const float* img,
                         const float* img3, int64_t B, void* out, void* stream);
 
+/* sad_backbone_run_keep for the deep plans: one chunk (B <= the micro-batch the
+ * workspace was sized for), exactly one of map and img non-null, feats
+ * [B, num_features] fp32, l4_out caller-owned [B, 16, 16, num_features] in the
+ * plan's activation layout (as above; SAD_BF16X3: 2 num_features bf16 per
+ * pixel).  The same note applies: the features are the pool of the stored,
+ * rounded activation (here the ordinary run pools it too). */
+int sad_resnet_run_keep(const sad_resnet_plan* plan, const float* map, const float* img, int64_t B,
+                        float* feats, void* l4_out, void* workspace, size_t ws_bytes, void* stream);
+
 /* Kernel-level timing of the backbone's block-conv launches (bench.py's
  * roofline of the dominant kernel): between begin and end, every block-conv
  * launch of sad_backbone_run* is bracketed by HIP events on its stream.  end()
@@ -493,6 +517,48 @@ int sad_heads_plan_info(const sad_heads_plan* plan, int32_t* grouped, int64_t* r
 int sad_heads_merge_run(const sad_heads_plan* plan, const float* const* feats, int64_t B,
                         float* logits, float* merged, void* workspace, size_t ws_bytes,
                         void* stream);
+
+/* --------------------------------------------------------------- evidence */
+/* Evidence maps: Grad-CAM of one head's target logit on its backbone's layer4
+ * activation, exact and without a backward pass through any conv (DESIGN.md
+ * 5e).  The reference has no counterpart; the model is the reference's
+ * (BinaryClassifier, inference_runner.py:36-51, eval mode).
+ *
+ * For window b and head h:  j = feat_index[h];  A = backbone j's layer4 output
+ * [16, 16, C] as sad_*_run_keep stores it (C = 512 or 2048, HW = 256);  f = the
+ * pooled features of the same run;  cls = 0 (Real) or 1 (Synthetic).
+ *   1. masks  m1 = (y1 > 0), m2 = (y2 > 0) from the head's own forward on f (a
+ *      unit at exactly 0 is off, as in torch's ReLU gradient);
+ *   2. g[b, h, :] = W1^T (m1 * (W2^T (m2 * W3[cls, :]))), fp32, W1 / W2 the
+ *      BN-folded weights as the heads plan holds them:  g = d logit[cls] / d f;
+ *   3. E[b, h, y, x] = (1 / HW) sum_c g[b, h, c] A[b, y, x, c]: signed, fp32,
+ *      unnormalised.  Positive E is evidence for the target; ReLU and scaling to
+ *      [0, 1] are display steps on the host.
+ * By construction sum_yx E[b, h] = g . f, and logit[cls] = g . f + beta(masks).
+ *
+ * sad_heads_grad_run: step 2 for every head, after sad_heads_merge_run on the
+ * same B rows.  workspace: merge_run's, untouched since (y1 / y2 in the layout
+ * above; only read).  g_out [n_heads][B][feat_dim] fp32.  Two GEMMs per head,
+ * (B x 256)(256 x 512) then (B x 512)(512 x feat_dim), on the f32 implicit-GEMM
+ * kernel, in row ranges as merge_run: a row's result does not depend on its
+ * position in the batch.  The transposed folded weights and one row range of
+ * scratch are allocated by the FIRST call on a plan (which also waits for
+ * `stream` once, so it cannot be graph-captured); a plan that never explains
+ * allocates nothing.  Calls on ONE plan share that scratch: they must not run
+ * concurrently on different streams. */
+int sad_heads_grad_run(const sad_heads_plan* plan, const void* workspace, int64_t B, int32_t cls, float* g_out,
+                       void* stream);
+/* Step 3 for the n_maps heads that read one backbone, in ONE pass over its
+ * activation.  l4 [B, hw, C] in the layout of `dtype` (sad_dtype; SAD_BF16X3:
+ * 2 C bf16 per pixel, value = hi + lo in fp32); g: n_maps HOST-array pointers
+ * to DEVICE [B][C] fp32 (g_out + h B feat_dim of sad_heads_grad_run);
+ * out [B][n_maps][hw] fp32.  fp32 accumulation in a fixed order, no atomics:
+ * the output is bit-reproducible and independent of B, of a window's position
+ * in the batch and of n_maps.  SAD_ERR_ARG before any launch for a null
+ * pointer (l4, g, any g[m], out), C not a positive multiple of 64, hw < 1,
+ * n_maps outside 1..16, or n_maps * C > 32768 (the gradients stay in LDS). */
+int sad_evidence_run(const void* l4, int32_t dtype, int64_t B, int32_t hw, int32_t C, const float* const* g,
+                     int32_t n_maps, float* out, void* stream);
 
 /* ------------------------------------------------------------- operators */
 /* One NHWC convolution (+ folded-BN bias, optional residual add, optional

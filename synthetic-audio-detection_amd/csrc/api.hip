@@ -44,6 +44,16 @@ struct sad_heads_plan {
   float* b2 = nullptr;             // [N][256]
   float* w3 = nullptr;             // [N][2][256]
   float* b3 = nullptr;             // [N][2]
+  // sad_heads_grad_run only, built on its first call (a plan that never explains allocates none of it)
+  struct Grad {
+    std::mutex mu;
+    bool built = false;
+    std::vector<float*> w1t;       // per head: [feat_dim][512] = folded W1 transposed
+    float* w2t = nullptr;          // [N][512][256] = folded W2 transposed
+    float* zero = nullptr;         // [max(512, feat_dim)] zero bias
+    float* scratch = nullptr;      // [kGradRows][256 + 512]: one row range's masked operands
+  };
+  mutable Grad grad;
 };
 
 extern "C" const char* sad_last_error(void) { return g_err.c_str(); }
@@ -616,6 +626,21 @@ extern "C" int sad_backbone_run_debug(const sad_backbone_plan* p, const float* m
   return run_chunk(p, map, nullptr, B, feats, layer4_out, (char*)ws, (hipStream_t)stream);
 }
 
+extern "C" int sad_backbone_run_keep(const sad_backbone_plan* p, const float* map, const float* img, int64_t B,
+                                     float* feats, void* l4_out, void* ws, size_t ws_bytes, void* stream) {
+  SAD_REQUIRE(p && feats && l4_out && ws, "run_keep: null plan, feats, l4_out or workspace");
+  SAD_REQUIRE((map != nullptr) != (img != nullptr), "run_keep: exactly one of map and img must be given");
+  SAD_REQUIRE(B >= 0, "run_keep: negative B");
+  if (B == 0) return SAD_OK;
+  size_t need = 0;
+  sad_backbone_workspace_size(p, B, &need);
+  if (ws_bytes < need) {
+    set_error("workspace too small (run_keep takes one chunk: B <= the micro-batch the workspace was sized for)");
+    return SAD_ERR_NOMEM;
+  }
+  return run_chunk(p, map, img, B, feats, l4_out, (char*)ws, (hipStream_t)stream);
+}
+
 extern "C" int sad_backbone_stem_run(const sad_backbone_plan* p, const float* map, int64_t B, void* out,
                                      void* stream) {
   SAD_REQUIRE(p && map && out && B >= 0, "null args");
@@ -759,6 +784,10 @@ extern "C" int sad_heads_plan_destroy(sad_heads_plan* p) {
   (void)hipFree(p->b2);
   (void)hipFree(p->w3);
   (void)hipFree(p->b3);
+  for (auto* w : p->grad.w1t) (void)hipFree(w);
+  (void)hipFree(p->grad.w2t);
+  (void)hipFree(p->grad.zero);
+  (void)hipFree(p->grad.scratch);
   delete p;
   return SAD_OK;
 }
@@ -871,6 +900,107 @@ extern "C" int sad_heads_merge_run(const sad_heads_plan* p, const float* const* 
     }
   }
   return launch_heads_final(y2, B, N, p->w3, p->b3, logits, merged, s);
+}
+
+// ---- head gradient (evidence maps): g = W1^T (m1 * (W2^T (m2 * W3[cls]))) per
+// head, as two GEMMs on the f32 implicit-GEMM kernel over the TRANSPOSED
+// folded weights, the ReLU masks taken from y1 / y2 as merge_run left them.
+static constexpr int64_t kGradRows = 4096;  // rows per range (whole tiles of every variant)
+
+static void heads_grad_free(const sad_heads_plan* p) {
+  auto& g = p->grad;
+  for (auto* w : g.w1t) (void)hipFree(w);
+  g.w1t.clear();
+  (void)hipFree(g.w2t);
+  (void)hipFree(g.zero);
+  (void)hipFree(g.scratch);
+  g.w2t = g.zero = g.scratch = nullptr;
+}
+
+static int heads_grad_build(const sad_heads_plan* p, hipStream_t s) {
+  auto& g = p->grad;
+  const int N = p->n_heads, D = p->feat_dim;
+  int rc;
+  const size_t nz = (size_t)std::max(512, D);
+  SAD_CHECK_HIP(hipMalloc((void**)&g.zero, nz * sizeof(float)));
+  SAD_CHECK_HIP(hipMemsetAsync(g.zero, 0, nz * sizeof(float), s));
+  SAD_CHECK_HIP(hipMalloc((void**)&g.scratch, (size_t)kGradRows * (256 + 512) * sizeof(float)));
+  SAD_CHECK_HIP(hipMalloc((void**)&g.w2t, (size_t)N * 512 * 256 * sizeof(float)));
+  for (int h = 0; h < N; ++h) {
+    if ((rc = launch_transpose(p->w2 + (size_t)h * 256 * 512, g.w2t + (size_t)h * 512 * 256, 256, 512, s))) return rc;
+    const auto& grp = p->groups[p->feat_index[h]];
+    size_t gi = 0;
+    while (grp[gi] != h) ++gi;
+    g.w1t.push_back(nullptr);
+    SAD_CHECK_HIP(hipMalloc((void**)&g.w1t.back(), (size_t)D * 512 * sizeof(float)));
+    if ((rc = launch_transpose(p->w1[p->feat_index[h]] + gi * 512 * D, g.w1t.back(), 512, D, s))) return rc;
+  }
+  // later calls may come on other streams: the transposes are complete when this returns
+  SAD_CHECK_HIP(hipStreamSynchronize(s));
+  return SAD_OK;
+}
+
+extern "C" int sad_heads_grad_run(const sad_heads_plan* p, const void* ws, int64_t B, int32_t cls, float* g_out,
+                                  void* stream) {
+  SAD_REQUIRE(p && ws && g_out, "heads grad: null plan, workspace or g_out");
+  SAD_REQUIRE(cls == 0 || cls == 1, "heads grad: cls must be 0 (Real) or 1 (Synthetic)");
+  SAD_REQUIRE(B >= 0, "heads grad: negative B");
+  if (B == 0) return SAD_OK;
+  hipStream_t s = (hipStream_t)stream;
+  {
+    std::lock_guard<std::mutex> lk(p->grad.mu);
+    if (!p->grad.built) {
+      if (int rc = heads_grad_build(p, s)) {
+        heads_grad_free(p);
+        return rc;
+      }
+      p->grad.built = true;
+    }
+  }
+  const int N = p->n_heads, D = p->feat_dim;
+  const float* y1 = (const float*)ws;
+  const float* y2 = y1 + (size_t)B * N * 512;
+  float* u2 = p->grad.scratch;
+  float* t1 = u2 + kGradRows * 256;
+  int rc;
+  for (int64_t r0 = 0; r0 < B; r0 += kGradRows) {
+    const int64_t rows = std::min(kGradRows, B - r0);
+    for (int h = 0; h < N; ++h) {
+      // u2 = m2 * W3[cls];  t1 = u2 W2;  t1 *= m1;  g = t1 W1
+      if ((rc = launch_relu_mask(y2 + r0 * N * 256 + h * 256, (int64_t)N * 256, p->w3 + h * 512 + cls * 256, u2, rows,
+                                 256, s)))
+        return rc;
+      ConvArgs a{};
+      a.in = u2;
+      a.in_pstride = 256;
+      a.N = (int)rows;
+      a.H = a.W = 1;
+      a.Cin = 256;
+      a.wt = p->grad.w2t + (size_t)h * 512 * 256;
+      a.bias = p->grad.zero;
+      a.out = t1;
+      a.out_pstride = 512;
+      a.Ho = a.Wo = 1;
+      a.Cout = 512;
+      a.KH = a.KW = 1;
+      a.stride = 1;
+      a.pad = 0;
+      a.relu = 0;
+      a.M = rows;
+      if ((rc = launch_conv(a, SAD_F32, s))) return rc;
+      if ((rc = launch_relu_mask(y1 + r0 * N * 512 + p->y1_col[h], (int64_t)N * 512, nullptr, t1, rows, 512, s)))
+        return rc;
+      a.in = t1;
+      a.in_pstride = 512;
+      a.Cin = 512;
+      a.wt = p->grad.w1t[h];
+      a.out = g_out + ((size_t)h * B + r0) * D;
+      a.out_pstride = D;
+      a.Cout = D;
+      if ((rc = launch_conv(a, SAD_F32, s))) return rc;
+    }
+  }
+  return SAD_OK;
 }
 
 // ------------------------------------------------------------- operators ----

@@ -140,6 +140,11 @@ int launch_col2im(const float* dcol, int64_t N, int H, int W, int C, int k, int 
 int launch_avgpool(const void* in, int64_t B, int hw, int c, float* out, int dtype, hipStream_t s);
 int launch_heads_final(const float* y2, int64_t B, int n_heads, const float* w3, const float* b3,
                        float* logits, float* merged, hipStream_t s);
+// sad_heads_grad_run's helpers (evidence.hip): out[r][c] = y[r * y_stride + c] > 0 ? (vec ? vec[c] : out[r][c]) : 0
+// on a dense [rows][cols] out, and dst [cols][rows] = src [rows][cols] transposed
+int launch_relu_mask(const float* y, int64_t y_stride, const float* vec, float* out, int64_t rows, int cols,
+                     hipStream_t s);
+int launch_transpose(const float* src, float* dst, int rows, int cols, hipStream_t s);
 
 // ---- host-side plan helpers (api.hip)
 template <typename V>

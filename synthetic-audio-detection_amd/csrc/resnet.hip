@@ -221,7 +221,7 @@ static int rn_block_conv(const sad_resnet_plan* p, const ConvW& c, const void* x
 }
 
 static int rn_chunk(const sad_resnet_plan* p, const float* map, const float* img, int64_t n, float* feats, char* ws,
-                    hipStream_t s, const float* img3 = nullptr) {
+                    hipStream_t s, const float* img3 = nullptr, void* l4_out = nullptr) {
   const size_t ab = rn_act_bytes(p, n);
   void* X = ws;
   void* Y = ws + ab;
@@ -251,6 +251,8 @@ static int rn_chunk(const sad_resnet_plan* p, const float* map, const float* img
     H = Ho;
     C = b.cout;
   }
+  if (l4_out)  // sad_resnet_run_keep: the last stage's activation as the pool reads it
+    SAD_CHECK_HIP(hipMemcpyAsync(l4_out, X, (size_t)n * H * H * C * dtype_bytes(p->dtype), hipMemcpyDeviceToDevice, s));
   return launch_avgpool(X, n, H * H, C, feats, p->dtype, s);
 }
 
@@ -272,6 +274,21 @@ static int rn_run(const sad_resnet_plan* p, const float* map, const float* img, 
     if (rc) return rc;
   }
   return SAD_OK;
+}
+
+extern "C" int sad_resnet_run_keep(const sad_resnet_plan* p, const float* map, const float* img, int64_t B,
+                                   float* feats, void* l4_out, void* ws, size_t ws_bytes, void* stream) {
+  SAD_REQUIRE(p && feats && l4_out && ws, "run_keep: null plan, feats, l4_out or workspace");
+  SAD_REQUIRE((map != nullptr) != (img != nullptr), "run_keep: exactly one of map and img must be given");
+  SAD_REQUIRE(B >= 0, "run_keep: negative B");
+  if (B == 0) return SAD_OK;
+  size_t need = 0;
+  sad_resnet_workspace_size(p, B, &need);
+  if (ws_bytes < need) {
+    set_error("workspace too small (run_keep takes one chunk: B <= the micro-batch the workspace was sized for)");
+    return SAD_ERR_NOMEM;
+  }
+  return rn_chunk(p, map, img, B, feats, (char*)ws, (hipStream_t)stream, nullptr, l4_out);
 }
 
 extern "C" int sad_resnet_stem_run(const sad_resnet_plan* p, const float* map, const float* img, const float* img3,

@@ -146,6 +146,17 @@ class ModularMultiHeadClassifier:
     def forward_maps(self, maps: torch.Tensor) -> torch.Tensor:
         return self.engine.forward_maps(maps.to(self.device).contiguous())[1]
 
+    def explain_maps(self, maps: torch.Tensor, target: str = 'synthetic'):
+        """maps [B, 128, 251] -> (merged [B, N+1], evidence [B, N, 16, 16]): Engine.explain."""
+        return self.engine.explain(maps.to(self.device).contiguous(), 'maps', target)
+
+    def explain_pcm(self, wav: torch.Tensor, target: str = 'synthetic'):
+        """[B, 128000] int16 PCM or fp32 waveform -> (merged [B, N+1], evidence
+        [B, N, 16, 16] fp32): per window and sub-model, which part of the window
+        (rows = mel bands, lowest first; columns = time) carried the target
+        logit ('synthetic', 'real' or 'margin'), signed and unnormalised."""
+        return self.engine.explain_pcm(wav.to(self.device).contiguous(), target)
+
     def __call__(self, x: torch.Tensor) -> torch.Tensor:
         """x: [B, 3, 512, 512] spectrogram images (the reference's model input)."""
         x = x.to(self.device, torch.float32)
@@ -362,6 +373,35 @@ def run_windows(model: ModularMultiHeadClassifier, chunks, sr: int, spec_cfg: Sp
     return torch.cat(outs)
 
 
+def explain_windows(model: ModularMultiHeadClassifier, chunks, sr: int, spec_cfg: SpectrogramConfig,
+                    batch_size: int = 128, target: str = 'synthetic') -> np.ndarray:
+    """Evidence maps of all windows of a sad.ingest.Windows -> [n, N, 16, 16]
+    float32 (host): a second pass over the windows, `batch_size` at a time."""
+    dev = model.device
+    fe = _frontend(dev, spec_cfg, chunks.window, sr)
+    wf = chunks.wf.to(dev)
+    offs = chunks.offsets.to(dev)
+    outs = []
+    for start in range(0, len(chunks), batch_size):
+        outs.append(model.explain_maps(fe.windows(wf, offs[start:start + batch_size]), target)[1].cpu())
+    return torch.cat(outs).numpy()
+
+
+def write_evidence(path: str, evidence: np.ndarray, timestamps, names, target: str, window_sec: float,
+                   fe) -> None:
+    """The --evidence sidecar: evidence [windows, N, 16, 16] float32, timestamps
+    (window starts, s), names (the sub-models' class names), target, col_sec
+    [16] (column starts within a window), row_hz [16, 2] (each row's lowest /
+    highest frequency with a non-zero mel weight, from the front end's
+    filterbank) and timeline [N, bins] (sad.evidence.timeline, float64)."""
+    from sad import evidence as _ev
+    with open(path, 'wb') as f:  # (np.savez would append '.npz' to a bare name)
+        np.savez(f, evidence=evidence.astype(np.float32), timestamps=np.asarray(timestamps, dtype=np.float64),
+                 names=np.asarray(list(names)), target=np.asarray(target), col_sec=_ev.col_sec(window_sec),
+                 row_hz=_ev.row_hz(fe.fbank.numpy(), fe.sample_rate),
+                 timeline=_ev.timeline(evidence, timestamps, window_sec))
+
+
 # 5. Main Inference Logic -------------------------------------------------------
 def build_parser() -> argparse.ArgumentParser:
     parser = argparse.ArgumentParser(
@@ -380,6 +420,12 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument('--batch-size', type=int, default=128, help='windows per device launch')
     parser.add_argument('--model-name', default='resnet18', choices=list(_weights.ARCHS),
                         help='backbone of the merged sub-models (the reference hard-codes resnet18, :77,246)')
+    parser.add_argument('--evidence', metavar='OUT.npz', default=None,
+                        help='also write per-window, per-sub-model evidence maps (Grad-CAM on layer4, computed on '
+                             'the device) to this .npz; the JSON and the labels do not change')
+    parser.add_argument('--evidence-target', choices=list(_engine.EXPLAIN_TARGETS), default='synthetic',
+                        help="the logit the evidence explains: each sub-model's Synthetic logit, its Real logit, "
+                             'or their margin (synthetic minus real)')
     return parser
 
 
@@ -421,6 +467,11 @@ def main(argv=None):
                          args.smooth, audio_cfg.window_size)
     with open(args.output_json, 'w', encoding='utf-8') as f:
         json.dump(out_json, f, indent=4)
+    if args.evidence:  # a second pass; everything above is the ordinary forward's
+        ev = explain_windows(model, chunks, sr, spec_cfg, args.batch_size, args.evidence_target)
+        write_evidence(args.evidence, ev, timestamps, synthetic_names, args.evidence_target, audio_cfg.window_size,
+                       _frontend(device, spec_cfg, chunks.window, sr))
+        print('Wrote evidence maps to', args.evidence)
     print('Wrote results to', args.output_json)
     print(json.dumps(out_json, indent=4))
     return out_json

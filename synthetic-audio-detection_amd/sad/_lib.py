@@ -117,6 +117,11 @@ SIGNATURES = {
     'sad_heads_workspace_size': (ctypes.c_int, [P, I64, ctypes.POINTER(SZ)]),
     'sad_heads_plan_info': (ctypes.c_int, [P, ctypes.POINTER(I32), ctypes.POINTER(I64)]),
     'sad_heads_merge_run':(ctypes.c_int, [P, FPP, I64, P, P, P, SZ, P]),
+    # evidence maps (include/sad.h "evidence")
+    'sad_backbone_run_keep': (ctypes.c_int, [P, P, P, I64, P, P, P, SZ, P]),
+    'sad_resnet_run_keep': (ctypes.c_int, [P, P, P, I64, P, P, P, SZ, P]),
+    'sad_heads_grad_run': (ctypes.c_int, [P, P, I64, I32, P, P]),
+    'sad_evidence_run': (ctypes.c_int, [P, I32, I64, I32, I32, FPP, I32, P, P]),
     'sad_conv2d_run': (ctypes.c_int, [P, I64, I32, I32, I32, P, P, P, P, I32, I32, I32, I32, I32, I32, I32, P]),
     'sad_block_conv_run': (ctypes.c_int, [P, I64, I32, I32, I32, P, I32, I32, I32, I32, P, I32, P, P, P, I32, I32,
                                           I32, I32, I32, I32, I32, P]),

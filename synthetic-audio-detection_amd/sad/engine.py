@@ -106,6 +106,7 @@ class FrontEnd:
         nf = _lib.I32()
         _lib.call('sad_frontend_frames', self._plan, _lib.ctypes.byref(nf))
         self.n_frames, self.n_mels, self.n_samples = nf.value, n_mels, n_samples
+        self.fbank, self.sample_rate = fb, sample_rate  # the plan's filterbank (sad.evidence.row_hz reads it)
 
     def __call__(self, pcm: torch.Tensor, want_db: bool = False, out: torch.Tensor | None = None):
         """pcm [n, >=n_samples] int16 (or fp32 waveform in [-1,1)) on device ->
@@ -335,6 +336,23 @@ class Backbone:
                       _lib.ptr(l4), _lib.ptr(ws), ws.numel(), _lib.stream_handle(self.device))
         return feats, (from_split(l4) if self.dtype == 'bf16x3' else l4)
 
+    def keep(self, x: torch.Tensor, kind: str = 'maps'):
+        """One chunk (B <= micro_batch) with the layer4 activation kept
+        (sad_backbone_run_keep): (feats [B,512] fp32, l4 NHWC [B,16,16,512] in
+        the plan's activation LAYOUT -- bf16x3: 1024 bf16 per pixel, not
+        decoded).  The features are the pool of the stored activation."""
+        mp, ip = self._input(x, kind)
+        B = x.shape[0]
+        if B > self.micro_batch:
+            raise ValueError(f'keep takes one chunk of at most micro_batch = {self.micro_batch} windows (got {B})')
+        feats = torch.empty(B, 512, device=self.device, dtype=torch.float32)
+        l4 = torch.empty(B, 16, 16, _act_channels(self.dtype, 512), device=self.device, dtype=self.tdtype)
+        ws = self.workspace(max(1, B))
+        with torch.cuda.device(self.device):
+            _lib.call('sad_backbone_run_keep', self._plan, mp, ip, B, _lib.ptr(feats), _lib.ptr(l4), _lib.ptr(ws),
+                      ws.numel(), _lib.stream_handle(self.device))
+        return feats, l4
+
     def __del__(self):
         try:
             if getattr(self, '_plan', None):
@@ -392,6 +410,32 @@ class ResNetBackbone:
         """img3 [B,3,512,512] fp32 with possibly distinct channels -> feats."""
         assert img3.dtype == torch.float32 and img3.shape[1:] == (3, 512, 512) and img3.is_contiguous()
         return self._run('sad_resnet_run_img3', img3, out)
+
+    def keep(self, x: torch.Tensor, kind: str = 'maps'):
+        """One chunk (B <= micro_batch) with the last stage's activation kept
+        (sad_resnet_run_keep): (feats [B,num_features] fp32, l4 NHWC
+        [B,16,16,num_features] in the plan's activation layout, bf16x3 not
+        decoded)."""
+        if kind not in ('maps', 'img'):
+            raise ValueError(f"kind must be 'maps' or 'img' (got {kind!r})")
+        shape = (MAP_H, MAP_W) if kind == 'maps' else (512, 512)
+        assert x.dtype == torch.float32 and x.shape[1:] == shape and x.is_contiguous() and x.device == self.device
+        B = x.shape[0]
+        if B > self.micro_batch:
+            raise ValueError(f'keep takes one chunk of at most micro_batch = {self.micro_batch} windows (got {B})')
+        nf = self.num_features
+        feats = torch.empty(B, nf, device=self.device, dtype=torch.float32)
+        l4 = torch.empty(B, 16, 16, _act_channels(self.dtype, nf), device=self.device,
+                         dtype=_tensor_dtype(self.dtype))
+        sz = _lib.SZ()
+        _lib.call('sad_resnet_workspace_size', self._plan, max(1, B), _lib.ctypes.byref(sz))
+        if self._ws is None or self._ws.numel() < sz.value:
+            self._ws = torch.empty(sz.value, dtype=torch.uint8, device=self.device)
+        mp, ip = (_lib.ptr(x), None) if kind == 'maps' else (None, _lib.ptr(x))
+        with torch.cuda.device(self.device):
+            _lib.call('sad_resnet_run_keep', self._plan, mp, ip, B, _lib.ptr(feats), _lib.ptr(l4),
+                      _lib.ptr(self._ws), self._ws.numel(), _lib.stream_handle(self.device))
+        return feats, l4
 
     def __del__(self):
         try:
@@ -460,7 +504,24 @@ class Heads:
         with torch.cuda.device(self.device):
             _lib.call('sad_heads_merge_run', self._plan, fp, B, _lib.ptr(logits), _lib.ptr(merged),
                       _lib.ptr(self._ws), self._ws.numel(), _lib.stream_handle(self.device))
+        self._ws_rows = B
         return logits, merged
+
+    def grad(self, B: int, cls: int, out: torch.Tensor | None = None) -> torch.Tensor:
+        """d logit[cls] / d features of every head for the B rows of the LAST
+        ``__call__`` (sad_heads_grad_run reads the ReLU masks from its
+        workspace): [n_heads, B, feat_dim] fp32.  cls: 0 Real, 1 Synthetic."""
+        if self._ws is None or getattr(self, '_ws_rows', None) != B:
+            raise RuntimeError(f'grad({B}) must follow a forward of the same {B} rows (the masks live in its workspace)')
+        if cls not in (0, 1):
+            raise ValueError(f'cls must be 0 (Real) or 1 (Synthetic), got {cls!r}')
+        g = out if out is not None else torch.empty(self.n_heads, B, self.feat_dim, device=self.device,
+                                                    dtype=torch.float32)
+        assert g.shape == (self.n_heads, B, self.feat_dim) and g.dtype == torch.float32 and g.is_contiguous()
+        with torch.cuda.device(self.device):
+            _lib.call('sad_heads_grad_run', self._plan, _lib.ptr(self._ws), B, cls, _lib.ptr(g),
+                      _lib.stream_handle(self.device))
+        return g
 
     def __del__(self):
         try:
@@ -468,6 +529,29 @@ class Heads:
                 _lib.load().sad_heads_plan_destroy(self._plan)
         except Exception:
             pass
+
+
+EXPLAIN_TARGETS = ('synthetic', 'real', 'margin')
+
+
+def evidence(l4: torch.Tensor, dtype: str, g: Sequence[torch.Tensor], out: torch.Tensor | None = None) -> torch.Tensor:
+    """sad_evidence_run: l4 NHWC [B, H, W, C'] in the activation layout of
+    `dtype` (C' = 2C for 'bf16x3'), g = 1..16 tensors [B, C] fp32 (one per map)
+    -> out [B, len(g), H*W] fp32, out[b, m, p] = sum_c g[m][b, c] A[b, p, c] / (H W)."""
+    B, hw = l4.shape[0], l4.shape[1] * l4.shape[2]
+    C = l4.shape[3] // (2 if dtype == 'bf16x3' else 1)
+    if l4.dtype != _tensor_dtype(dtype) or not l4.is_contiguous():
+        raise ValueError(f'l4 must be contiguous {_tensor_dtype(dtype)} for dtype {dtype!r}')
+    for t in g:
+        if t.dtype != torch.float32 or tuple(t.shape) != (B, C) or not t.is_contiguous() or t.device != l4.device:
+            raise ValueError(f'every g must be a contiguous fp32 [{B}, {C}] tensor on {l4.device}')
+    if out is None:
+        out = torch.empty(B, len(g), hw, device=l4.device, dtype=torch.float32)
+    gp = (_lib.ctypes.c_void_p * len(g))(*[t.data_ptr() for t in g])
+    with torch.cuda.device(l4.device):
+        _lib.call('sad_evidence_run', _lib.ptr(l4), _dtype_code(dtype), B, hw, C, gp, len(g), _lib.ptr(out),
+                  _lib.stream_handle(l4.device))
+    return out
 
 
 def _arch(base_sd) -> str:
@@ -615,6 +699,49 @@ class Engine:
 
     def forward_maps(self, maps: torch.Tensor):
         return self.heads(self.features(maps))
+
+    def explain(self, x: torch.Tensor, kind: str = 'maps', target: str = 'synthetic', details: list | None = None):
+        """Evidence maps (include/sad.h "evidence"): (merged [B, N+1], evidence
+        [B, N, 16, 16] fp32), evidence[b, h] = Grad-CAM of head h's target logit
+        on its backbone's layer4 activation: signed, unnormalised, rows = mel
+        axis (row 0 the lowest bands), columns = time.  target: 'synthetic',
+        'real', or 'margin' (synthetic minus real; the two share their masks).
+
+        Runs per micro-batch chunk: keep (every distinct backbone in full, a
+        shared trunk included), the heads on the chunk, their gradient, one
+        evidence pass per backbone -- a row of the heads does not depend on its
+        position in the batch, so the chunks are the whole batch's rows.  Only
+        one chunk's activations are alive at a time.  merged comes from the
+        keep path (features pooled from the stored activation), which can
+        differ from ``forward_maps`` by the activation rounding.
+        details (tests): a list that receives per chunk (rows, feats per
+        backbone, l4 per backbone, g per class, the heads' y1 | y2 workspace)."""
+        if target not in EXPLAIN_TARGETS:
+            raise ValueError(f'target must be one of {EXPLAIN_TARGETS} (got {target!r})')
+        B, N = x.shape[0], self.n_heads
+        merged = torch.empty(B, N + 1, device=self.device, dtype=torch.float32)
+        out = torch.empty(B, N, 16, 16, device=self.device, dtype=torch.float32)
+        mb = max(1, min(bb.micro_batch for bb in self.backbones))
+        readers = [[h for h in range(N) if self.grouping.feat_index[h] == j] for j in range(len(self.backbones))]
+        if any(len(r) > 16 for r in readers):
+            raise ValueError('explain: more than 16 heads read one backbone (sad_evidence_run takes 1..16 maps)')
+        for i in range(0, B, mb):
+            xi = x[i:i + mb]
+            n = xi.shape[0]
+            kept = [bb.keep(xi, kind) for bb in self.backbones]
+            self.heads([f for f, _ in kept], merged=merged[i:i + n])
+            gs = [self.heads.grad(n, cls) for cls in {'synthetic': (1,), 'real': (0,), 'margin': (1, 0)}[target]]
+            for j, (_, l4) in enumerate(kept):
+                ev = [evidence(l4, self.dtype, [g[h] for h in readers[j]]) for g in gs]
+                e = ev[0] - ev[1] if target == 'margin' else ev[0]
+                out[i:i + n, readers[j]] = e.view(n, len(readers[j]), 16, 16)
+            if details is not None:
+                y = self.heads._ws[:n * N * 768 * 4].view(torch.float32).clone()  # the chunk's y1 | y2
+                details.append((slice(i, i + n), [f for f, _ in kept], [a for _, a in kept], gs, y))
+        return merged, out
+
+    def explain_pcm(self, pcm: torch.Tensor, target: str = 'synthetic'):
+        return self.explain(self.frontend(pcm), 'maps', target)
 
     def forward_pcm(self, pcm: torch.Tensor):
         return self.forward_maps(self.frontend(pcm))
