@@ -242,6 +242,76 @@ int sad_train_ingest_run(const void* arena, int64_t arena_bytes, const int64_t* 
                          const sad_resample_plan* const* rate_plans, int32_t n_rates, int64_t seg_len, float* out,
                          void* stream);
 
+/* --------------------------------------------------------------- streaming */
+/* Live feeds (sad/stream.py, stream_runner.py): the ingestion above, formed
+ * chunk by chunk for many feeds in ONE launch per push, with the resampler's
+ * state carried across chunk boundaries.  For any way of cutting a recording
+ * into chunks the samples are the bits sad_pcm_mono_run + sad_resample_run give
+ * on the whole recording.
+ *
+ * A stream bank of `slots` slots is caller-owned device memory (like every
+ * workspace of this library), sized by sad_stream_bank_size:
+ *   arena [slots][2 CAP] fp32  per slot a mirrored ring of mono samples at the
+ *         target rate: global sample g sits at g mod CAP and at CAP + g mod CAP,
+ *         so up to CAP consecutive samples are contiguous from g mod CAP on and
+ *         sad_scan_select_run / sad_frontend_run_windows read windows in place
+ *         (wav = arena, wav_len = arena_len).  CAP = window + room, room =
+ *         max(4 max_chunk_frames, 4096), rounded up to a multiple of 4.
+ *   carry [slots][2][8192] fp32  the resampler's state: the mono-mixed input
+ *         samples the next push's taps reach back to (fewer than K), double-
+ *         buffered by push parity, because within one launch some workgroups of
+ *         a slot read the old carry while another writes the new one.
+ * Neither needs initialising: only what a push has written is ever read.
+ *
+ * Emission rule (rates reduced by their gcd to orig -> new; width, K as in the
+ * resample plan).  With F frames of a feed present, the outputs whose taps are
+ * all present are those of polyphase frames j < J(F) = (F - width) / orig (0
+ * for F < width): a push from F0 to F1 frames stores global samples
+ * [J(F0) new, J(F1) new); at the target rate it stores [F0, F1).  A final push
+ * stores the rest up to n_out = ceil(new F1 / orig) (missing inputs are zeros)
+ * and then zeros up to one window (preprocess_waveform's pad).  A feed opened
+ * at start_frame = J0 orig counts everything before it as digital silence and
+ * stores nothing below g0 = J0 new.
+ *
+ * sad_stream_open_check: may a feed of this rate and channel count, starting at
+ * start_frame, use a bank of this geometry?  Refuses channels outside 1..64, a
+ * rate the batched kernel cannot take (the rule of sad_train_ingest_file_tiles,
+ * or more than 8192 taps), a rate whose single polyphase frame plus end-of-feed
+ * tail exceed CAP - window, window > CAP, a start_frame that is no multiple of
+ * orig, and one whose first sample g0 (returned in *first_sample) is no
+ * multiple of hop.
+ *
+ * sad_stream_push_tiles: the workgroups of one table row, and (optionally) the
+ * global sample range [*first_out, *end_out) the row stores.
+ *
+ * sad_stream_push_run: one launch for all rows.  The chunks sit as stored
+ * (interleaved int16 / fp32) in one byte arena.  table [n_rows][10] int64:
+ *   0 slot (each slot at most once per launch)
+ *   1 byte offset of the chunk (a multiple of 16)    2 its frames (may be 0)
+ *   3 absolute frames of the feed before this chunk (>= start frame)
+ *   4 final (0 / 1)      5 index into rate_plans     6 channels (1..64)
+ *   7 sad_pcm_format     8 the feed's start frame    9 push parity (0 / 1: the
+ *     carry buffer to READ; the other one is written; the host flips it after
+ *     every launch that names the slot)
+ * tiles [n_tiles][2] int32: (row, tile), tile = 0 .. sad_stream_push_tiles - 1,
+ * in any order.  rate_plans as for sad_train_ingest_run (NULL = target rate).
+ * The host is the authority on every counter: the device mutates only arena
+ * and carry.  A row may add at most CAP - window samples (the caller splits a
+ * longer chunk).  table is read on the HOST for the argument checks; d_table
+ * and d_tiles are DEVICE copies.  Asynchronous on `stream`: one launch, no
+ * allocation, no atomics, no host synchronisation. */
+int sad_stream_bank_size(int64_t slots, int64_t window, int64_t hop, int64_t max_chunk_frames,
+                         int32_t target_rate, int64_t* cap, int64_t* arena_len, int64_t* carry_len);
+int sad_stream_open_check(int32_t rate, int32_t target_rate, int32_t channels, int64_t window, int64_t hop,
+                          int64_t cap, int64_t start_frame, int64_t* first_sample);
+int sad_stream_push_tiles(int32_t rate, int32_t target_rate, int64_t start_frame, int64_t frames_before,
+                          int64_t n_frames, int32_t final, int64_t window, int64_t* first_out, int64_t* end_out,
+                          int64_t* n_tiles);
+int sad_stream_push_run(const void* chunks, int64_t chunk_bytes, const int64_t* table, const int64_t* d_table,
+                        int64_t n_rows, const int32_t* d_tiles, int64_t n_tiles,
+                        const sad_resample_plan* const* rate_plans, int32_t n_rates, float* arena, float* carry,
+                        int64_t slots, int64_t cap, int64_t window, void* stream);
+
 /* --------------------------------------------------------- catalogue scan */
 /* Many files in one run (sad/scan.py, catalog_runner.py): the files' mono
  * 32 kHz waveforms sit back to back in ONE fp32 arena; the device picks the

@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "ingest.hpp"
 
 namespace sad {
 
@@ -87,7 +88,7 @@ __global__ __launch_bounds__(256) void resample_kernel(const float* __restrict__
 // tap's coefficient kt[k][p] is one coalesced load (the table stays in L2), and
 // each tap costs RS_R FMAs per lane.  The sum runs over k in the same order as
 // resample_kernel, so the two give identical results.
-constexpr int RS_R = 16, RS_KC = 64, RS_WAVES = 4;
+// (RS_R = 16 frames per wave, RS_KC = 64 taps per chunk, RS_WAVES = 4: ingest.hpp)
 __global__ __launch_bounds__(256) void resample_wide_kernel(const float* __restrict__ x, int64_t n_in,
                                                             const float* __restrict__ kt, int orig, int nw, int width,
                                                             int K, float* __restrict__ y, int64_t n_out) {
@@ -176,28 +177,13 @@ static unsigned grid_for(int64_t n) {
 //             inputs they need are mixed into LDS once, each thread sums K taps;
 //   wide      (nw >= 64: 44.1 / 22.05 kHz) resample_wide_kernel's blocking, 64
 //             frames x 64 phases per tile, the mono mix done while staging.
-constexpr int TI_TILE = 1024;     // outputs per tile, native and per-output forms
-constexpr int TI_SPAN = 8192;     // LDS floats: the per-output form's input span
-constexpr int TI_MAX_RATES = 8;   // distinct sample rates in one launch
+// (TI_TILE = 1024 outputs per tile, TI_SPAN = 8192 LDS floats, TI_MAX_RATES = 8: ingest.hpp)
 constexpr int TI_COLS = 6;        // file table columns
-static_assert(TI_SPAN >= RS_WAVES * RS_KC * RS_R, "the wide form's staging fits the span buffer");
 
 struct TrainRates {
   const float* kt[TI_MAX_RATES];  // nullptr: the target rate itself
   int orig[TI_MAX_RATES], nw[TI_MAX_RATES], width[TI_MAX_RATES], K[TI_MAX_RATES];
 };
-
-// pcm_mono_kernel's value at frame i; 0 outside the frames that were read
-template <typename IT>
-__device__ __forceinline__ float ti_mono(const IT* __restrict__ x, int64_t i, int64_t n_read, int channels,
-                                         float fc) {
-  const float scale = sizeof(IT) == 2 ? (1.0f / 32768.0f) : 1.0f;
-  if (i < 0 || i >= n_read) return 0.f;
-  const IT* p = x + i * channels;
-  float s = (float)p[0] * scale;
-  for (int c = 1; c < channels; ++c) s += (float)p[c] * scale;
-  return channels == 1 ? s : s / fc;
-}
 
 template <typename IT>
 __device__ __forceinline__ void ti_tile(float* __restrict__ xs, const IT* __restrict__ x, int64_t n_read,
@@ -308,34 +294,6 @@ __global__ __launch_bounds__(256) void train_ingest_kernel(const unsigned char* 
     ti_tile<float>(xs, (const float*)x, n_read, n_out, channels, kt, orig, nw, width, K, tile, seg_len, out0);
 }
 
-// torchaudio's polyphase geometry for orig_freq -> new_freq (sinc_interp_hann,
-// lowpass_filter_width 6, rolloff 0.99): rates reduced by their gcd, the filter
-// half-width in input samples and the taps per output
-struct RsGeometry {
-  int orig, nw, width, K;
-  double base;
-};
-
-static int64_t gcd64(int64_t a, int64_t b) {
-  while (b) {
-    const int64_t t = a % b;
-    a = b;
-    b = t;
-  }
-  return a;
-}
-
-static RsGeometry rs_geometry(int32_t orig_freq, int32_t new_freq) {
-  const int64_t g = gcd64(orig_freq, new_freq);
-  RsGeometry q;
-  q.orig = (int)(orig_freq / g);
-  q.nw = (int)(new_freq / g);
-  q.base = (double)(q.orig < q.nw ? q.orig : q.nw) * 0.99;
-  q.width = (int)ceil(6 * (double)q.orig / q.base);
-  q.K = 2 * q.width + q.orig;
-  return q;
-}
-
 // tiles of one file (0 when the form cannot take the rate: the per-output
 // form's input span must fit TI_SPAN)
 static int64_t ti_file_tiles(bool native, const RsGeometry& q, int64_t total_frames, int64_t seg_len) {
@@ -343,7 +301,7 @@ static int64_t ti_file_tiles(bool native, const RsGeometry& q, int64_t total_fra
   const int64_t M = n_out < 2 * seg_len ? seg_len : 2 * seg_len;
   if (native) return (M + TI_TILE - 1) / TI_TILE;
   if (q.nw < 64) {
-    if (((int64_t)(TI_TILE - 1) / q.nw + 1) * q.orig + q.K > TI_SPAN) return 0;
+    if (!rs_per_output_fits(q)) return 0;
     return (M + TI_TILE - 1) / TI_TILE;
   }
   const int64_t frames = (M + q.nw - 1) / q.nw;
@@ -353,13 +311,6 @@ static int64_t ti_file_tiles(bool native, const RsGeometry& q, int64_t total_fra
 }  // namespace sad
 
 using namespace sad;
-
-struct sad_resample_plan {
-  int32_t orig_freq = 0, new_freq = 0;
-  int orig = 1, nw = 1, width = 0, K = 0;  // reduced by the gcd
-  float* d_kt = nullptr;                    // [K][nw] fp32
-  int device = 0;
-};
 
 extern "C" int sad_pcm_mono_run(const void* pcm, int32_t format, int64_t frames, int32_t channels, float* out,
                                 int64_t out_len, void* stream) {

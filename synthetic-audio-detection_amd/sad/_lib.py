@@ -80,6 +80,13 @@ SIGNATURES = {
     'sad_train_ingest_need_frames': (ctypes.c_int, [I32, I32, I64, ctypes.POINTER(I64)]),
     'sad_train_ingest_file_tiles': (ctypes.c_int, [I32, I32, I64, I64, ctypes.POINTER(I64)]),
     'sad_train_ingest_run': (ctypes.c_int, [P, I64, P, P, I64, P, I64, FPP, I32, I64, P, P]),
+    # streaming (include/sad.h "streaming")
+    'sad_stream_bank_size': (ctypes.c_int, [I64, I64, I64, I64, I32, ctypes.POINTER(I64), ctypes.POINTER(I64),
+                                            ctypes.POINTER(I64)]),
+    'sad_stream_open_check': (ctypes.c_int, [I32, I32, I32, I64, I64, I64, I64, ctypes.POINTER(I64)]),
+    'sad_stream_push_tiles': (ctypes.c_int, [I32, I32, I64, I64, I64, I32, I64, ctypes.POINTER(I64),
+                                             ctypes.POINTER(I64), ctypes.POINTER(I64)]),
+    'sad_stream_push_run': (ctypes.c_int, [P, I64, P, P, I64, P, I64, FPP, I32, P, P, I64, I64, I64, P]),
     # catalogue scan (include/sad.h "catalogue scan")
     'sad_scan_select_workspace_size': (ctypes.c_int, [I64, I64, ctypes.POINTER(SZ)]),
     'sad_scan_select_run': (ctypes.c_int, [P, I64, P, P, I64, I64, I64, ctypes.c_float, I64, P, P, P, SZ, P]),

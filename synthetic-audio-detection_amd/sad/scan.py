@@ -160,9 +160,11 @@ def assemble_records(filenames: Sequence[str], file_start, row_start, offsets, l
 
 
 def select_windows_arena(arena: torch.Tensor, file_start: torch.Tensor, file_len: torch.Tensor, window: int,
-                         hop: int, silence_threshold: float, max_candidates: int):
+                         hop: int, silence_threshold: float, max_candidates: int,
+                         offsets: Optional[torch.Tensor] = None):
     """sad_scan_select_run on device tensors -> (offsets [max_candidates] int64,
-    row_start [n_files + 1] int64), both on the device; nothing is synchronised."""
+    row_start [n_files + 1] int64), both on the device; nothing is synchronised.
+    `offsets`: the tensor to fill (entries past the kept count keep their values)."""
     dev = arena.device
     assert arena.dtype == torch.float32 and arena.dim() == 1 and arena.is_contiguous()
     for t in (file_start, file_len):
@@ -172,7 +174,10 @@ def select_windows_arena(arena: torch.Tensor, file_start: torch.Tensor, file_len
     sz = _lib.SZ()
     _lib.call('sad_scan_select_workspace_size', n, int(max_candidates), _lib.ctypes.byref(sz))
     ws = torch.empty(max(sz.value, 8), dtype=torch.uint8, device=dev)
-    offsets = torch.empty(int(max_candidates), dtype=torch.int64, device=dev)
+    if offsets is None:
+        offsets = torch.empty(int(max_candidates), dtype=torch.int64, device=dev)
+    assert offsets.dtype == torch.int64 and offsets.is_contiguous() and offsets.device == dev
+    assert offsets.shape[0] >= int(max_candidates)
     row_start = torch.empty(n + 1, dtype=torch.int64, device=dev)
     with torch.cuda.device(dev):
         _lib.call('sad_scan_select_run', _lib.ptr(arena), arena.shape[0], _lib.ptr(file_start), _lib.ptr(file_len), n,
