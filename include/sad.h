@@ -242,6 +242,66 @@ int sad_train_ingest_run(const void* arena, int64_t arena_bytes, const int64_t* 
                          const sad_resample_plan* const* rate_plans, int32_t n_rates, int64_t seg_len, float* out,
                          void* stream);
 
+/* -------------------------------------------------- waveform augmentation */
+/* Six of the eleven kinds of the reference's audio_augmneter.py (:79-137, the
+ * clip of :190), one kind per file, applied to a batch that already sits in
+ * sad_train_ingest_run's byte arena (submodel_trainer.py --wave-augment).  The
+ * float64 contract is tests/waveaug_ref.py.  y is the file's mono mix
+ * (sad_pcm_mono_run's value, operation for operation; 0 past the frames
+ * present), sr its stored rate, L its total frames:
+ *   0 original                    y
+ *   1 dynamic_range_compression   sign(y) |y|^p0                       p0 > 0
+ *   2 add_white_noise             y_i + p0 rms n_i; rms over the frames written,
+ *                                 n_i a standard normal of (key, i) alone: the
+ *                                 splitmix64 finaliser of key + 0x9E3779B97F4A7C15 (i + 1),
+ *                                 u1 = (top 24 bits + 1) / 2^24, u2 = bits 16..39 / 2^24,
+ *                                 n = sqrt(-2 ln u1) cos(2 pi u2)
+ *   3 tremolo                     y ((1 - p1) + p1 sin(2 pi p0 t_i)), t = linspace(0, L / sr, L)
+ *   4 phaser                      lfo_i = p1 sin(2 pi p0 i / sr); for f0 = 500, 1500, 2500 Hz:
+ *                                 y <- y + lfo lfilter([al, 0, -al], [1 + al, -2 cos w, 1 - al], y),
+ *                                 w = 2 pi f0 / sr, al = sin(w) / 2; refused for sr <= 5000
+ *   5 time_shift                  out_i = y_{i - s} if s != 0 and 0 <= i - s < L, else 0;
+ *                                 s = p0, a whole number of frames (s = 0: all zeros, as
+ *                                 the reference gives)
+ * then clip(., -1, 1).  Left out: speed_up, slow_down, pitch_up, pitch_down and
+ * time_pitch_shift (a phase vocoder and a resampler of librosa's).  Deviations
+ * from the reference's tool: no resample to 44.1 kHz before augmenting, no round
+ * trip through a 16-bit stereo file after it, the rms over the frames written
+ * instead of the whole file, and this generator instead of numpy's.
+ *
+ * file_table [n_files][6] int64 and the arena: as for sad_train_ingest_run
+ * (column 5 is not read).  aug_table [n_files][8] int64, one row per file:
+ *   0 kind   1 sample rate (Hz)   2 frames to write, n_out <= total frames
+ *   3 byte offset of the file's output in mono_out (a multiple of 16, ascending)
+ *   4 p0 | p1: two fp32 values, p0 in the low 32 bits   5 the noise key
+ *   6 the sum of ceil(n_out / chunk) over the earlier files   7 reserved
+ * mono_out holds per file its first n_out frames, fp32, augmented and clipped;
+ * sad_train_ingest_run then reads it through a second file table (SAD_PCM_F32, one
+ * channel, n_out frames present, the same total), for which its mono mix is the
+ * identity: a file of kind 0 gives the rows it gives without this call, bit for
+ * bit (int16 files; fp32 files within [-1, 1]).
+ *
+ * Both tables are read on the HOST for the argument checks; d_file_table and
+ * d_aug_table are DEVICE copies (uploaded with the arena).  ws: caller-owned,
+ * 16-byte aligned, sad_wave_augment_workspace_size bytes.  At most seven
+ * launches for any batch (csrc/waveaug.hip says which), no allocation, no
+ * atomics, no host synchronisation; asynchronous on `stream`.  A file's output
+ * does not depend on the other files.  sad_wave_augment_geometry: the phaser
+ * scan's chunk (frames per workgroup) and the frames a lane walks serially. */
+int sad_wave_augment_geometry(int32_t* chunk, int32_t* sub);
+int sad_wave_augment_workspace_size(const int64_t* aug_table, int64_t n_files, size_t* bytes);
+int sad_wave_augment_run(const void* arena, int64_t arena_bytes, const int64_t* file_table,
+                         const int64_t* d_file_table, int64_t n_files, const int64_t* aug_table,
+                         const int64_t* d_aug_table, void* mono_out, int64_t mono_bytes, void* ws, size_t ws_bytes,
+                         void* stream);
+/* The phaser files of the same batch as ONE THREAD PER FILE walking the three
+ * stages serially (the other kinds are left alone): the yardstick that
+ * tools/bench_wave_augment.py times the chunked scan against.  Same tables,
+ * same checks, one launch, no workspace. */
+int sad_wave_phaser_serial_run(const void* arena, int64_t arena_bytes, const int64_t* file_table,
+                               const int64_t* d_file_table, int64_t n_files, const int64_t* aug_table,
+                               const int64_t* d_aug_table, void* mono_out, int64_t mono_bytes, void* stream);
+
 /* --------------------------------------------------------------- streaming */
 /* Live feeds (sad/stream.py, stream_runner.py): the ingestion above, formed
  * chunk by chunk for many feeds in ONE launch per push, with the resampler's

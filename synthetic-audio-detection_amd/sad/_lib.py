@@ -80,6 +80,11 @@ SIGNATURES = {
     'sad_train_ingest_need_frames': (ctypes.c_int, [I32, I32, I64, ctypes.POINTER(I64)]),
     'sad_train_ingest_file_tiles': (ctypes.c_int, [I32, I32, I64, I64, ctypes.POINTER(I64)]),
     'sad_train_ingest_run': (ctypes.c_int, [P, I64, P, P, I64, P, I64, FPP, I32, I64, P, P]),
+    # waveform augmentation (include/sad.h "waveform augmentation")
+    'sad_wave_augment_geometry': (ctypes.c_int, [ctypes.POINTER(I32), ctypes.POINTER(I32)]),
+    'sad_wave_augment_workspace_size': (ctypes.c_int, [P, I64, ctypes.POINTER(SZ)]),
+    'sad_wave_augment_run': (ctypes.c_int, [P, I64, P, P, I64, P, P, P, I64, P, SZ, P]),
+    'sad_wave_phaser_serial_run': (ctypes.c_int, [P, I64, P, P, I64, P, P, P, I64, P]),
     # streaming (include/sad.h "streaming")
     'sad_stream_bank_size': (ctypes.c_int, [I64, I64, I64, I64, I32, ctypes.POINTER(I64), ctypes.POINTER(I64),
                                             ctypes.POINTER(I64)]),

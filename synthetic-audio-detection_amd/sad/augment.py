@@ -68,3 +68,67 @@ def random_resized_crop_params(height: int = 512, width: int = 512, scale=CROP_S
 
 FULL_IMAGE = (0, 0, 512, 512)
 NO_MASK = (0, 0, 0, 0)
+
+
+# ------------------------------------------------------- waveform augmentation
+# submodel_trainer.py --wave-augment: the reference's audio_augmneter.py writes
+# eleven variants of every recording to disk ahead of training; here one kind is
+# drawn per file and per visit and applied on the device (csrc/waveaug.hip).  The
+# index of a name in WAVE_KINDS is the library's kind code (include/sad.h).
+WAVE_KINDS = ('original', 'dynamic_range_compression', 'add_white_noise', 'tremolo', 'phaser', 'time_shift')
+# librosa's phase vocoder and its soxr resampler: not rebuilt
+WAVE_UNSUPPORTED = ('speed_up', 'slow_down', 'pitch_up', 'pitch_down', 'time_pitch_shift')
+WAVE_PHASER_MIN_SR = 5000   # the phaser's 2500 Hz stage leaves the unit circle at and below this rate
+WAVE_SHIFT_MARGIN = 0.5     # seconds: the largest |shift| (audio_augmneter.py:129)
+# the reference's ranges (audio_augmneter.py:79-129)
+WAVE_RANGES = {'amount': (0.01, 0.5), 'vol': (0.001, 0.05), 'trem_rate': (3.0, 6.0), 'trem_depth': (0.2, 0.5),
+               'ph_depth': (0.5, 0.9), 'ph_rate': (0.1, 1.0), 'shift': (-0.5, 0.5)}
+
+
+def parse_wave_kinds(text: str):
+    """'all' or comma-separated names out of WAVE_KINDS -> tuple of names, in
+    WAVE_KINDS' order, each once.  ValueError names the supported set."""
+    supported = ', '.join(WAVE_KINDS)
+    names = [n.strip() for n in str(text).split(',') if n.strip()]
+    if not names:
+        raise ValueError(f'no augmentation kind given; supported: {supported}, or all')
+    if names == ['all']:
+        return WAVE_KINDS
+    for n in names:
+        if n in WAVE_UNSUPPORTED:
+            raise ValueError(f'{n} is not supported (librosa\'s phase vocoder and resampler are not rebuilt); '
+                             f'supported: {supported}')
+        if n not in WAVE_KINDS:
+            raise ValueError(f'unknown augmentation kind {n!r}; supported: {supported}')
+    return tuple(k for k in WAVE_KINDS if k in names)
+
+
+def _uniform(lo_hi, generator):
+    return torch.empty(1).uniform_(lo_hi[0], lo_hi[1], generator=generator).item()
+
+
+def wave_aug_params(kinds, sr: int, generator: torch.Generator | None = None):
+    """One draw for one file: a kind uniformly from `kinds` (a file at or below
+    WAVE_PHASER_MIN_SR draws among the others), then that kind's parameters from
+    the reference's ranges, in the reference's order -> (kind code, p0, p1, key):
+    (amount) | (vol, key) | (rate, depth) | (rate, depth), depth drawn first | (s),
+    s = int(shift * sr) frames."""
+    cands = [k for k in kinds if k != 'phaser' or sr > WAVE_PHASER_MIN_SR] or ['original']
+    # (a single candidate needs no draw: --wave-augment original draws nothing at all)
+    kind = cands[int(torch.randint(0, len(cands), (1,), generator=generator).item())] if len(cands) > 1 else cands[0]
+    p0 = p1 = 0.0
+    key = 0
+    if kind == 'dynamic_range_compression':
+        p0 = _uniform(WAVE_RANGES['amount'], generator)
+    elif kind == 'add_white_noise':
+        p0 = _uniform(WAVE_RANGES['vol'], generator)
+        key = int(torch.randint(-2 ** 63, 2 ** 63 - 1, (1,), dtype=torch.int64, generator=generator).item())
+    elif kind == 'tremolo':
+        p0 = _uniform(WAVE_RANGES['trem_rate'], generator)
+        p1 = _uniform(WAVE_RANGES['trem_depth'], generator)
+    elif kind == 'phaser':
+        p1 = _uniform(WAVE_RANGES['ph_depth'], generator)
+        p0 = _uniform(WAVE_RANGES['ph_rate'], generator)
+    elif kind == 'time_shift':
+        p0 = float(int(_uniform(WAVE_RANGES['shift'], generator) * sr))
+    return WAVE_KINDS.index(kind), p0, p1, key

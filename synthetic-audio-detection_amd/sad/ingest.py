@@ -17,7 +17,11 @@ per-window maxima (the same fp32 comparison as ``piece.abs().max() < thr``).
 
 The trainer's batched twin is at the end of the module ("trainer ingestion"):
 stored samples of a whole batch -> the [2B, seg_len] training segments in one
-upload and one launch (``TrainIngest``, ``collate_stored``).
+upload and one launch (``TrainIngest``, ``collate_stored``).  With waveform
+augmentation rows (``submodel_trainer.py --wave-augment``) the same upload also
+carries one augmentation row per file, and a stage in front of that launch
+(``sad_wave_augment_run``, csrc/waveaug.hip) writes an augmented fp32 mono arena
+that the unchanged launch then reads.
 """
 from __future__ import annotations
 
@@ -181,6 +185,9 @@ TRAIN_SPAN = 8192      # TI_SPAN: the per-output form's input span in LDS
 TRAIN_MAX_RATES = 8    # TI_MAX_RATES: distinct source rates in one launch
 TRAIN_COLS = 6         # file table columns (include/sad.h "trainer ingestion")
 TRAIN_WIDE_FRAMES = 64  # RS_WAVES * RS_R: frames per tile of the wide form
+WAVE_SUB = 32          # WA_SUB (csrc/waveaug.hip): frames a lane walks serially
+WAVE_CHUNK = 2048      # WA_CHUNK: frames per workgroup, the phaser scan's chunk
+WAVE_COLS = 8          # augmentation table columns (include/sad.h "waveform augmentation")
 
 
 def resample_geometry(sr: int, target_sr: int = 32000):
@@ -244,14 +251,17 @@ def train_rate_supported(sr: int, target_sr: int = 32000) -> bool:
 class StoredFile:
     """One training file as its DataLoader worker leaves it: the first
     `frames_read` frames as stored (int16, or fp32 decoded from another
-    encoding), the header's metadata, the label and the augmentation rows."""
-    __slots__ = ('samples', 'frames_read', 'frames', 'channels', 'sr', 'target', 'aug')
+    encoding), the header's metadata, the label and the augmentation rows.
+    `wave` is the file's waveform augmentation draw (kind code, p0, p1, key:
+    sad.augment.wave_aug_params), or None without --wave-augment."""
+    __slots__ = ('samples', 'frames_read', 'frames', 'channels', 'sr', 'target', 'aug', 'wave')
 
-    def __init__(self, samples: np.ndarray, frames: int, channels: int, sr: int, target: int, aug: torch.Tensor):
+    def __init__(self, samples: np.ndarray, frames: int, channels: int, sr: int, target: int, aug: torch.Tensor,
+                 wave=None):
         assert samples.dtype in (np.int16, np.float32) and samples.ndim == 1
         self.samples, self.frames, self.channels, self.sr = samples, int(frames), int(channels), int(sr)
         self.frames_read = samples.shape[0] // self.channels
-        self.target, self.aug = int(target), aug
+        self.target, self.aug, self.wave = int(target), aug, wave
 
 
 class StoredBatch:
@@ -259,12 +269,20 @@ class StoredBatch:
     files' samples, each starting at a multiple of 16 bytes, then the file
     table [n_files, 6] int64 and the tile table [n_tiles, 2] int32
     (include/sad.h "trainer ingestion").  `rates[i]` is the sample rate behind
-    rate index i; targets int64 [B]; aug int32 [B, 2, 8]."""
+    rate index i; targets int64 [B]; aug int32 [B, 2, 8].
 
-    def __init__(self, arena, n_files, n_tiles, table_off, tiles_off, rates, targets, aug, seg_len):
+    With waveform augmentation (a file drew another kind than 'original') the
+    arena also carries, at wave_off, the augmentation table [n_files, 8] int64
+    and, at mono_table_off, the file table of the fp32 mono arena that
+    sad_wave_augment_run writes (mono_bytes long; made on the device, never
+    uploaded); both offsets are None otherwise."""
+
+    def __init__(self, arena, n_files, n_tiles, table_off, tiles_off, rates, targets, aug, seg_len,
+                 wave_off=None, mono_table_off=None, mono_bytes=0):
         self.arena, self.n_files, self.n_tiles = arena, int(n_files), int(n_tiles)
         self.table_off, self.tiles_off = int(table_off), int(tiles_off)
         self.rates, self.targets, self.aug, self.seg_len = tuple(rates), targets, aug, int(seg_len)
+        self.wave_off, self.mono_table_off, self.mono_bytes = wave_off, mono_table_off, int(mono_bytes)
 
     @property
     def table(self) -> torch.Tensor:
@@ -274,6 +292,17 @@ class StoredBatch:
     @property
     def tiles(self) -> torch.Tensor:
         return self.arena[self.tiles_off:self.tiles_off + 8 * self.n_tiles].view(torch.int32).view(self.n_tiles, 2)
+
+    def _rows(self, off, cols) -> torch.Tensor:
+        return self.arena[off:off + 8 * cols * self.n_files].view(torch.int64).view(self.n_files, cols)
+
+    @property
+    def wave_table(self) -> torch.Tensor:
+        return self._rows(self.wave_off, WAVE_COLS)
+
+    @property
+    def mono_table(self) -> torch.Tensor:
+        return self._rows(self.mono_table_off, TRAIN_COLS)
 
     def pin_memory(self):
         """DataLoader(pin_memory=True) calls this: the arena is the upload."""
@@ -313,13 +342,52 @@ def collate_stored(files, seg_len: int = 128000, target_sr: int = 32000):
     tiles = np.concatenate(tiles)
     table_off = off
     tiles_off = _align(table_off + table.nbytes)
-    buf = np.zeros(_align(tiles_off + tiles.nbytes), np.uint8)
+    end = _align(tiles_off + tiles.nbytes)
+    wave = _wave_tables(files, table, seg_len, target_sr)
+    extra = {}
+    if wave is not None:  # a batch of 'original' draws is the plain path
+        wave_table, mono_table, mono_bytes = wave
+        extra = dict(wave_off=end, mono_table_off=_align(end + wave_table.nbytes), mono_bytes=mono_bytes)
+        end = _align(extra['mono_table_off'] + mono_table.nbytes)
+    buf = np.zeros(end, np.uint8)
     for row, f in zip(table, files):
         buf[row[0]:row[0] + f.samples.nbytes] = f.samples.view(np.uint8)
     buf[table_off:table_off + table.nbytes] = table.reshape(-1).view(np.uint8)
     buf[tiles_off:tiles_off + tiles.nbytes] = tiles.reshape(-1).view(np.uint8)
+    if wave is not None:
+        buf[extra['wave_off']:extra['wave_off'] + wave_table.nbytes] = wave_table.reshape(-1).view(np.uint8)
+        o = extra['mono_table_off']
+        buf[o:o + mono_table.nbytes] = mono_table.reshape(-1).view(np.uint8)
     return StoredBatch(torch.from_numpy(buf), len(files), tiles.shape[0], table_off, tiles_off, rates,
-                       torch.tensor([f.target for f in files]), torch.stack([f.aug for f in files]), seg_len)
+                       torch.tensor([f.target for f in files]), torch.stack([f.aug for f in files]), seg_len, **extra)
+
+
+def wave_chunks(n_out: int) -> int:
+    return -(-int(n_out) // WAVE_CHUNK)
+
+
+def _wave_tables(files, table, seg_len, target_sr):
+    """(augmentation table [B, 8], the mono arena's file table [B, 6], the mono
+    arena's bytes) of include/sad.h "waveform augmentation", or None when every
+    file drew 'original' (kind 0) or none has a draw.  File f's output holds its
+    first min(total, need) frames: what the two segments read."""
+    if all(f.wave is None or f.wave[0] == 0 for f in files):
+        return None
+    wave = np.zeros((len(files), WAVE_COLS), np.int64)
+    mono = np.zeros((len(files), TRAIN_COLS), np.int64)
+    off = chunks = 0
+    for i, f in enumerate(files):
+        kind, p0, p1, key = f.wave if f.wave is not None else (0, 0.0, 0.0, 0)
+        n_out = min(f.frames, f.frames_read, train_need_frames(f.sr, seg_len, target_sr))
+        params = np.array([p0, p1], np.float32).view(np.uint32).astype(np.uint64)
+        wave[i, :4] = (kind, f.sr, n_out, off)
+        wave[i, 4:6] = np.array([params[0] | (params[1] << np.uint64(32)), int(key) & 0xFFFFFFFFFFFFFFFF],
+                                np.uint64).view(np.int64)
+        wave[i, 6] = chunks
+        mono[i] = (off, n_out, f.frames, 1, _lib.SAD_PCM_F32, table[i, 5])
+        off = _align(off + 4 * n_out)
+        chunks += wave_chunks(n_out)
+    return wave, mono, off
 
 
 class TrainIngest:
@@ -350,10 +418,29 @@ class TrainIngest:
         out = torch.empty(2 * batch.n_files, batch.seg_len, device=dev, dtype=torch.float32)
         base = d_arena.data_ptr()
         with torch.cuda.device(dev):
-            _lib.call('sad_train_ingest_run', base, batch.table_off, batch.table.data_ptr(), base + batch.table_off,
+            src, src_bytes, table, d_table = base, batch.table_off, batch.table, base + batch.table_off
+            if batch.wave_off is not None:  # stage one: augment into an fp32 mono arena, then ingest that
+                mono = self.wave_augment(batch, d_arena)
+                src, src_bytes, table, d_table = mono.data_ptr(), batch.mono_bytes, batch.mono_table, \
+                    base + batch.mono_table_off
+            _lib.call('sad_train_ingest_run', src, src_bytes, table.data_ptr(), d_table,
                       batch.n_files, base + batch.tiles_off, batch.n_tiles, plans, len(batch.rates), batch.seg_len,
                       _lib.ptr(out), _lib.stream_handle(dev))
         return out
+
+    def wave_augment(self, batch: StoredBatch, d_arena: torch.Tensor) -> torch.Tensor:
+        """sad_wave_augment_run on an uploaded batch: the fp32 mono arena (uint8
+        [mono_bytes]; file f at batch.wave_table[f, 3], batch.wave_table[f, 2] frames)."""
+        dev, base = self.device, d_arena.data_ptr()
+        need = _lib.SZ()
+        _lib.call('sad_wave_augment_workspace_size', batch.wave_table.data_ptr(), batch.n_files, ctypes.byref(need))
+        mono = torch.empty(max(batch.mono_bytes, 16), device=dev, dtype=torch.uint8)
+        ws = torch.empty(max(need.value, 16), device=dev, dtype=torch.uint8)
+        with torch.cuda.device(dev):
+            _lib.call('sad_wave_augment_run', base, batch.table_off, batch.table.data_ptr(), base + batch.table_off,
+                      batch.n_files, batch.wave_table.data_ptr(), base + batch.wave_off, mono.data_ptr(),
+                      batch.mono_bytes, ws.data_ptr(), need.value, _lib.stream_handle(dev))
+        return mono
 
     def segments(self, batch: StoredBatch) -> torch.Tensor:
         """The rows in the host path's order: every file's first segment, then

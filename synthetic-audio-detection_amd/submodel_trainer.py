@@ -56,6 +56,17 @@ Differences (documented in DESIGN.md / INTEGRATION.md):
     an extension over the host path: 2-64 channel files are mixed to mono as
     the inference path does instead of being skipped.  Its workers come from a
     fork server and persist across epochs (get_dataloaders says why).
+  * ``--wave-augment LIST`` (with ``--device-ingest``; off by default): the
+    reference trains on a tree that ``audio_augmneter.py`` wrote ahead of time,
+    eleven variants per recording.  With the flag the train split draws, per
+    file and per epoch, one kind out of LIST (original,
+    dynamic_range_compression, add_white_noise, tremolo, phaser, time_shift, or
+    ``all``) with parameters from the reference's ranges, and the device applies
+    it to the stored samples before they are resampled (csrc/waveaug.hip,
+    sad_wave_augment_run).  The five librosa kinds (speed_up, slow_down,
+    pitch_up, pitch_down, time_pitch_shift) are refused.  Not reproduced: the
+    tool's resample to 44.1 kHz, its 16-bit file round trip, numpy's normal
+    generator; the noise's RMS runs over the frames read.
   * TensorBoard is optional (not installed here): scalars are logged instead.
 """
 from __future__ import annotations
@@ -128,7 +139,24 @@ def parse_args(argv=None):
                              'Same segments and augmentation draws as the default host path (bit-identical for '
                              '32 kHz mono files).  An extension over the host path: files of 2-64 channels are mixed '
                              'to mono as the inference path does, where the host path skips them with a warning')
+    parser.add_argument('--wave-augment', default='', type=str, metavar='LIST',
+                        help='waveform augmentation of the train split on the device (needs --device-ingest): per file '
+                             'and per epoch one kind is drawn uniformly from LIST, with parameters from the ranges of '
+                             'the reference\'s audio_augmneter.py, and applied to the stored samples before they are '
+                             f'resampled.  LIST: comma-separated names out of {", ".join(_augment.WAVE_KINDS)}, or '
+                             f'all.  Not supported: {", ".join(_augment.WAVE_UNSUPPORTED)}.  Validation and '
+                             '--evaluate are never augmented')
     args = parser.parse_args(argv)
+    if args.wave_augment:
+        if not args.device_ingest:
+            parser.error('--wave-augment needs --device-ingest: the augmentation runs on the stored samples that '
+                         'the device ingestion uploads')
+        try:
+            args.wave_augment = _augment.parse_wave_kinds(args.wave_augment)
+        except ValueError as e:
+            parser.error(f'--wave-augment: {e}')
+    else:
+        args.wave_augment = None
     if args.trunk:
         if args.model_name != 'resnet18':
             parser.error(f'--trunk needs --model-name resnet18 (got {args.model_name}): the frozen trunk runs on '
@@ -245,7 +273,14 @@ class StoredSampleDataset(SpectrogramDataset):
     WAV header alone, reads only the frames the two segments need, as stored,
     and returns a ``sad.ingest.StoredFile`` (or None); the device resamples
     and cuts the segments (``sad.ingest.TrainIngest``).  Unlike the host path
-    it takes files of 1-64 channels (mixed to mono as the inference path does)."""
+    it takes files of 1-64 channels (mixed to mono as the inference path does).
+
+    ``wave_kinds`` (``--wave-augment``; None = off, and then nothing below
+    differs): a tuple of names out of ``sad.augment.WAVE_KINDS``.  Per visit one
+    kind and its parameters are drawn AFTER the SpecAugment and crop draws, so
+    those read the same as without the flag; with ``time_shift`` in the list the
+    worker reads half a second more, the samples a left shift brings in."""
+    wave_kinds = None
 
     def __getitem__(self, index):
         from sad import ingest as _ingest
@@ -265,11 +300,14 @@ class StoredSampleDataset(SpectrogramDataset):
                               f"Required: {2 * SEGMENT_LENGTH}")
                 return None
             need = _ingest.train_need_frames(sample_rate, SEGMENT_LENGTH, 32000)
+            if self.wave_kinds and 'time_shift' in self.wave_kinds:
+                need += int(_augment.WAVE_SHIFT_MARGIN * sample_rate)
             samples, _, _ = _audio.read_wav(path, max_frames=min(frames, need))
             if samples.shape[0] != min(frames, need) * channels:
                 raise ValueError('the data chunk is shorter than its header says')
             aug = self._aug_params()
-            return _ingest.StoredFile(samples, frames, channels, sample_rate, target, aug)
+            wave = _augment.wave_aug_params(self.wave_kinds, sample_rate) if self.wave_kinds else None
+            return _ingest.StoredFile(samples, frames, channels, sample_rate, target, aug, wave)
         except Exception as e:
             logging.warning(f"Error processing file at index {index}, path {path}: {str(e)}")
             return None
@@ -502,6 +540,8 @@ def get_dataloaders(args, rank: int = 0, world: int = 1):
     collate = stored_collate_fn if stored else custom_collate_fn
     train_dataset = dataset_cls(args.data_dir, 'train', transform='train', class_names=[args.Class0, args.Class1])
     val_dataset = dataset_cls(args.data_dir, 'test', transform='val', class_names=[args.Class0, args.Class1])
+    if stored and getattr(args, 'wave_augment', None):  # the train split only
+        train_dataset.wave_kinds = tuple(args.wave_augment)
     per_rank = args.batch_size if world > 1 else (args.batch_size * args.num_gpus if args.num_gpus > 0
                                                    else args.batch_size)
     logging.info(f"Total batch size: {per_rank * world}")
