@@ -263,8 +263,9 @@ int sad_train_ingest_run(const void* arena, int64_t arena_bytes, const int64_t* 
  *   5 time_shift                  out_i = y_{i - s} if s != 0 and 0 <= i - s < L, else 0;
  *                                 s = p0, a whole number of frames (s = 0: all zeros, as
  *                                 the reference gives)
- * then clip(., -1, 1).  Left out: speed_up, slow_down, pitch_up, pitch_down and
- * time_pitch_shift (a phase vocoder and a resampler of librosa's).  Deviations
+ * then clip(., -1, 1).  speed_up, slow_down, pitch_up, pitch_down and
+ * time_pitch_shift are kinds 6-10 of sad_wave_stretch_run ("time and pitch"
+ * below), not of these entries.  Deviations
  * from the reference's tool: no resample to 44.1 kHz before augmenting, no round
  * trip through a 16-bit stereo file after it, the rms over the frames written
  * instead of the whole file, and this generator instead of numpy's.
@@ -301,6 +302,85 @@ int sad_wave_augment_run(const void* arena, int64_t arena_bytes, const int64_t* 
 int sad_wave_phaser_serial_run(const void* arena, int64_t arena_bytes, const int64_t* file_table,
                                const int64_t* d_file_table, int64_t n_files, const int64_t* aug_table,
                                const int64_t* d_aug_table, void* mono_out, int64_t mono_bytes, void* stream);
+
+/* ---------------------------------------------------------- time and pitch */
+/* The other five kinds of audio_augmneter.py (:55-76, :140-145, the clip of
+ * :190), the ones that go through librosa (submodel_trainer.py --wave-stretch,
+ * csrc/stretch.hip).  The float64 contract is tests/stretch_ref.py: librosa's
+ * documented time_stretch and pitch_shift restated (n_fft 2048, hop 512,
+ * periodic Hann, center = True with zero padding), NOT pinned to librosa:
+ *   time_stretch(y, r) = istft(phase_vocoder(stft(y), r), round(len(y) / r))
+ *   pitch_shift(y, n)  = resample_ratio(time_stretch(y, q), q, len(y)), q = 2^(-n / 12)
+ *   6 speed_up, 7 slow_down     time_stretch(y, rate)
+ *   8 pitch_up, 9 pitch_down    pitch_shift(y, steps)
+ *   10 time_pitch_shift         pitch_shift(time_stretch(y, rate), steps)
+ * then clip(., -1, 1).  Deviations from the reference's tool: no resample to
+ * 44.1 kHz first, no 16-bit file round trip, and resample_ratio, the
+ * ingestion's Hann-windowed sinc (width 6, rolloff 0.99) at an arbitrary ratio
+ *   out[i] = sum_j x[j] h(i / rho - j), h(u) = c sinc(c u) cos^2(pi u c / 12), |u| < 6 / c,
+ *   c = 0.99 min(1, rho)
+ * in the place of librosa's soxr_hq.
+ *
+ * Four stage entries, each batched over files through a stage table
+ * [n_files][8] int64 (read on the HOST for the checks; d_table is its DEVICE copy):
+ *   0 byte offset of the file's input in `in`     1 input count
+ *   2 byte offset of its output in `out`          3 output count
+ *   4 the rate, a float64's bits (vocoder, resample; within [0.25, 4])
+ *   5 flags: 1 = clip the output to [-1, 1] (istft, resample)
+ *   6 byte offset of the file's workspace in `ws` (vocoder, istft)   7 reserved
+ * Offsets are multiples of 16 and ascend without overlap.  Counts:
+ *   stft      in: fp32 samples present (0 past them); out: frames [T][1025] complex
+ *             fp32, frame f = samples [512 f - 1024, 512 f + 1024); the caller
+ *             gives T = 1 + length / 512 or fewer
+ *   vocoder   in: frames present (0 past them); out: the steps t < count, step t at
+ *             s = t rate (float64) reads frames int(s), int(s) + 1; the phase is a
+ *             Q0.32 fraction of a turn, summed over the steps by a chunked scan
+ *             of 32-bit integers (sad_wave_stretch_geometry's chunk)
+ *   istft     in: frames available, of which the first ceil((length + 2048) / 512)
+ *             are read; out: `length` fp32 samples (count), zero past the frames
+ *   resample  in: fp32 samples; out: count samples at ratio rho = column 4
+ * Asynchronous on `stream`, caller-owned workspace (the *_workspace_size entries),
+ * no atomics, no allocation. */
+int sad_wave_stretch_geometry(int32_t* n_fft, int32_t* hop, int32_t* chunk, int32_t* max_launches);
+int sad_stft2048_run(const void* in, int64_t in_bytes, const int64_t* table, const int64_t* d_table,
+                     int64_t n_files, void* out, int64_t out_bytes, void* stream);
+int sad_phase_vocoder_workspace_size(const int64_t* table, int64_t n_files, size_t* bytes);
+int sad_phase_vocoder_run(const void* in, int64_t in_bytes, const int64_t* table, const int64_t* d_table,
+                          int64_t n_files, void* out, int64_t out_bytes, void* ws, size_t ws_bytes, void* stream);
+int sad_istft2048_workspace_size(const int64_t* table, int64_t n_files, size_t* bytes);
+int sad_istft2048_run(const void* in, int64_t in_bytes, const int64_t* table, const int64_t* d_table,
+                      int64_t n_files, void* out, int64_t out_bytes, void* ws, size_t ws_bytes, void* stream);
+int sad_resample_ratio_run(const void* in, int64_t in_bytes, const int64_t* table, const int64_t* d_table,
+                           int64_t n_files, void* out, int64_t out_bytes, void* stream);
+/* The batch entry.  arena and file_table [n_files][6]: as for sad_train_ingest_run
+ * (column 1 = frames present, column 2 = total frames L; column 5 is not read).
+ * stretch_table [n_files][8] int64, one row per file:
+ *   0 kind: 6..10 above; 0..5 = a file of sad_wave_augment_run, left alone here
+ *   1 rate, a float64's bits (kinds 6, 7, 10), within [0.25, 4]
+ *   2 steps, a float64's bits (kinds 8, 9, 10), |steps| <= 12
+ *   3 frames to write, n_out <= the kind's output length (round(L / rate); L for 8, 9)
+ *   4 byte offset of the file's output in mono_out (a multiple of 16, ascending)
+ *   5 the pitch rate 2^(-steps / 12), a float64's bits (kinds 8, 9, 10): every
+ *     length on the host and on the device derives from these bits
+ *   6, 7 reserved
+ * The file is mono-mixed as sad_pcm_mono_run does (0 past the frames present),
+ * goes through its kind's chain and is clipped; mono_out receives its first
+ * n_out frames in the layout sad_wave_augment_run writes, so both entries fill one
+ * arena that sad_train_ingest_run reads through its second file table.  Only
+ * what the first n_out frames depend on is computed (tests/stretch_ref.py
+ * need_frames says how much of the file that is).  For every file the result is,
+ * bit for bit, what sad_pcm_mono_run and the stage entries give one after
+ * another on that file alone: the entry runs the same kernels on stage tables
+ * that one more kernel derives on the device.  At most 17 launches for any batch
+ * (plan, mono mix, 7 per stretch x 2, resample); ws: 16-byte aligned,
+ * sad_wave_stretch_workspace_size bytes.  Everything else is refused with
+ * SAD_ERR_ARG before any launch. */
+int sad_wave_stretch_workspace_size(const int64_t* file_table, const int64_t* stretch_table, int64_t n_files,
+                                    size_t* bytes);
+int sad_wave_stretch_run(const void* arena, int64_t arena_bytes, const int64_t* file_table,
+                         const int64_t* d_file_table, int64_t n_files, const int64_t* stretch_table,
+                         const int64_t* d_stretch_table, void* mono_out, int64_t mono_bytes, void* ws,
+                         size_t ws_bytes, void* stream);
 
 /* --------------------------------------------------------------- streaming */
 /* Live feeds (sad/stream.py, stream_runner.py): the ingestion above, formed

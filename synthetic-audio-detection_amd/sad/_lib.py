@@ -85,6 +85,16 @@ SIGNATURES = {
     'sad_wave_augment_workspace_size': (ctypes.c_int, [P, I64, ctypes.POINTER(SZ)]),
     'sad_wave_augment_run': (ctypes.c_int, [P, I64, P, P, I64, P, P, P, I64, P, SZ, P]),
     'sad_wave_phaser_serial_run': (ctypes.c_int, [P, I64, P, P, I64, P, P, P, I64, P]),
+    # time and pitch (include/sad.h "time and pitch")
+    'sad_wave_stretch_geometry': (ctypes.c_int, [ctypes.POINTER(I32)] * 4),
+    'sad_stft2048_run': (ctypes.c_int, [P, I64, P, P, I64, P, I64, P]),
+    'sad_phase_vocoder_workspace_size': (ctypes.c_int, [P, I64, ctypes.POINTER(SZ)]),
+    'sad_phase_vocoder_run': (ctypes.c_int, [P, I64, P, P, I64, P, I64, P, SZ, P]),
+    'sad_istft2048_workspace_size': (ctypes.c_int, [P, I64, ctypes.POINTER(SZ)]),
+    'sad_istft2048_run': (ctypes.c_int, [P, I64, P, P, I64, P, I64, P, SZ, P]),
+    'sad_resample_ratio_run': (ctypes.c_int, [P, I64, P, P, I64, P, I64, P]),
+    'sad_wave_stretch_workspace_size': (ctypes.c_int, [P, P, I64, ctypes.POINTER(SZ)]),
+    'sad_wave_stretch_run': (ctypes.c_int, [P, I64, P, P, I64, P, P, P, I64, P, SZ, P]),
     # streaming (include/sad.h "streaming")
     'sad_stream_bank_size': (ctypes.c_int, [I64, I64, I64, I64, I32, ctypes.POINTER(I64), ctypes.POINTER(I64),
                                             ctypes.POINTER(I64)]),

@@ -76,7 +76,7 @@ NO_MASK = (0, 0, 0, 0)
 # drawn per file and per visit and applied on the device (csrc/waveaug.hip).  The
 # index of a name in WAVE_KINDS is the library's kind code (include/sad.h).
 WAVE_KINDS = ('original', 'dynamic_range_compression', 'add_white_noise', 'tremolo', 'phaser', 'time_shift')
-# librosa's phase vocoder and its soxr resampler: not rebuilt
+# the kinds of librosa's phase vocoder: not kinds of --wave-augment but of --wave-stretch (STRETCH_KINDS below)
 WAVE_UNSUPPORTED = ('speed_up', 'slow_down', 'pitch_up', 'pitch_down', 'time_pitch_shift')
 WAVE_PHASER_MIN_SR = 5000   # the phaser's 2500 Hz stage leaves the unit circle at and below this rate
 WAVE_SHIFT_MARGIN = 0.5     # seconds: the largest |shift| (audio_augmneter.py:129)
@@ -96,8 +96,7 @@ def parse_wave_kinds(text: str):
         return WAVE_KINDS
     for n in names:
         if n in WAVE_UNSUPPORTED:
-            raise ValueError(f'{n} is not supported (librosa\'s phase vocoder and resampler are not rebuilt); '
-                             f'supported: {supported}')
+            raise ValueError(f'{n} is not supported here (it is a kind of --wave-stretch); supported: {supported}')
         if n not in WAVE_KINDS:
             raise ValueError(f'unknown augmentation kind {n!r}; supported: {supported}')
     return tuple(k for k in WAVE_KINDS if k in names)
@@ -132,3 +131,58 @@ def wave_aug_params(kinds, sr: int, generator: torch.Generator | None = None):
     elif kind == 'time_shift':
         p0 = float(int(_uniform(WAVE_RANGES['shift'], generator) * sr))
     return WAVE_KINDS.index(kind), p0, p1, key
+
+
+# ------------------------------------------------------------ time and pitch
+# submodel_trainer.py --wave-stretch: the five kinds that change tempo and pitch
+# (csrc/stretch.hip; the float64 contract is tests/stretch_ref.py).  Kind codes
+# continue WAVE_KINDS': STRETCH_CODE0 + the index in STRETCH_KINDS.
+STRETCH_KINDS = WAVE_UNSUPPORTED
+STRETCH_CODE0 = len(WAVE_KINDS)
+# the reference's ranges (audio_augmneter.py:55-76, 140-145)
+STRETCH_RANGES = {'speed_up': (1.0, 1.5), 'slow_down': (0.5, 1.0), 'pitch_up': (0.0, 2.0), 'pitch_down': (-2.0, 0.0),
+                  'tps_rate': (0.8, 1.2), 'tps_steps': (-1.0, 1.0)}
+
+
+def parse_stretch_kinds(text: str):
+    """'all' or comma-separated names out of STRETCH_KINDS -> tuple of names, in
+    STRETCH_KINDS' order, each once.  ValueError names the supported set."""
+    supported = ', '.join(STRETCH_KINDS)
+    names = [n.strip() for n in str(text).split(',') if n.strip()]
+    if not names:
+        raise ValueError(f'no stretch kind given; supported: {supported}, or all')
+    if names == ['all']:
+        return STRETCH_KINDS
+    for n in names:
+        if n in WAVE_KINDS:
+            raise ValueError(f'{n} is a kind of --wave-augment; supported here: {supported}')
+        if n not in STRETCH_KINDS:
+            raise ValueError(f'unknown stretch kind {n!r}; supported: {supported}')
+    return tuple(k for k in STRETCH_KINDS if k in names)
+
+
+def stretch_aug_params(kind: str, generator: torch.Generator | None = None):
+    """The parameters of one stretch kind from the reference's ranges, in the
+    reference's order -> (kind code, p0, p1, 0): (rate) | (steps) | (rate, steps),
+    the rate drawn first."""
+    p1 = 0.0
+    if kind == 'time_pitch_shift':
+        p0 = _uniform(STRETCH_RANGES['tps_rate'], generator)
+        p1 = _uniform(STRETCH_RANGES['tps_steps'], generator)
+    else:
+        p0 = _uniform(STRETCH_RANGES[kind], generator)
+    return STRETCH_CODE0 + STRETCH_KINDS.index(kind), p0, p1, 0
+
+
+def wave_stretch_params(wave_kinds, stretch_kinds, sr: int, generator: torch.Generator | None = None):
+    """One draw for one file with --wave-stretch: a kind uniformly from the union
+    of both lists (a file at or below WAVE_PHASER_MIN_SR draws among the others),
+    then that kind's parameters -> (kind code, p0, p1, key) as wave_aug_params
+    gives them.  Without stretch kinds this is wave_aug_params, draw for draw."""
+    if not stretch_kinds:
+        return wave_aug_params(wave_kinds, sr, generator)
+    cands = [k for k in tuple(wave_kinds or ()) if k != 'phaser' or sr > WAVE_PHASER_MIN_SR] + list(stretch_kinds)
+    kind = cands[int(torch.randint(0, len(cands), (1,), generator=generator).item())] if len(cands) > 1 else cands[0]
+    if kind in STRETCH_KINDS:
+        return stretch_aug_params(kind, generator)
+    return wave_aug_params((kind,), sr, generator)   # (a one-kind list draws no kind)

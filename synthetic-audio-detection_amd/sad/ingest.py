@@ -21,7 +21,9 @@ upload and one launch (``TrainIngest``, ``collate_stored``).  With waveform
 augmentation rows (``submodel_trainer.py --wave-augment``) the same upload also
 carries one augmentation row per file, and a stage in front of that launch
 (``sad_wave_augment_run``, csrc/waveaug.hip) writes an augmented fp32 mono arena
-that the unchanged launch then reads.
+that the unchanged launch then reads.  Files that drew a time-stretch or
+pitch-shift kind (``--wave-stretch``) go through ``sad_wave_stretch_run``
+(csrc/stretch.hip) into the same arena.
 """
 from __future__ import annotations
 
@@ -34,6 +36,7 @@ import torch
 
 from . import _lib
 from . import audio as _audio
+from . import augment as _augment
 
 
 def _dev(device) -> torch.device:
@@ -188,6 +191,10 @@ TRAIN_WIDE_FRAMES = 64  # RS_WAVES * RS_R: frames per tile of the wide form
 WAVE_SUB = 32          # WA_SUB (csrc/waveaug.hip): frames a lane walks serially
 WAVE_CHUNK = 2048      # WA_CHUNK: frames per workgroup, the phaser scan's chunk
 WAVE_COLS = 8          # augmentation table columns (include/sad.h "waveform augmentation")
+STRETCH_CODE0 = _augment.STRETCH_CODE0   # the first kind code of sad_wave_stretch_run (include/sad.h "time and pitch")
+# sad_wave_stretch_geometry (tests/test_stretch_reference.py ties them to the library): n_fft, hop, the
+# vocoder scan's chunk in output frames, the batch entry's launch bound
+STRETCH_N_FFT, STRETCH_HOP, STRETCH_CHUNK, STRETCH_MAX_LAUNCHES = 2048, 512, 64, 17
 
 
 def resample_geometry(sr: int, target_sr: int = 32000):
@@ -278,11 +285,12 @@ class StoredBatch:
     uploaded); both offsets are None otherwise."""
 
     def __init__(self, arena, n_files, n_tiles, table_off, tiles_off, rates, targets, aug, seg_len,
-                 wave_off=None, mono_table_off=None, mono_bytes=0):
+                 wave_off=None, mono_table_off=None, mono_bytes=0, stretch_off=None):
         self.arena, self.n_files, self.n_tiles = arena, int(n_files), int(n_tiles)
         self.table_off, self.tiles_off = int(table_off), int(tiles_off)
         self.rates, self.targets, self.aug, self.seg_len = tuple(rates), targets, aug, int(seg_len)
         self.wave_off, self.mono_table_off, self.mono_bytes = wave_off, mono_table_off, int(mono_bytes)
+        self.stretch_off = stretch_off  # the stretch table [n_files, 8] (a file drew a kind >= 6), or None
 
     @property
     def table(self) -> torch.Tensor:
@@ -299,6 +307,10 @@ class StoredBatch:
     @property
     def wave_table(self) -> torch.Tensor:
         return self._rows(self.wave_off, WAVE_COLS)
+
+    @property
+    def stretch_table(self) -> torch.Tensor:
+        return self._rows(self.stretch_off, WAVE_COLS)
 
     @property
     def mono_table(self) -> torch.Tensor:
@@ -332,7 +344,7 @@ def collate_stored(files, seg_len: int = 128000, target_sr: int = 32000):
     table = np.zeros((len(files), TRAIN_COLS), np.int64)
     tiles, off = [], 0
     for i, f in enumerate(files):
-        nt = train_file_tiles(f.sr, f.frames, seg_len, target_sr)
+        nt = train_file_tiles(f.sr, _out_frames(f), seg_len, target_sr)
         if nt <= 0:
             raise ValueError(f'sample rate {f.sr} Hz is not supported by the batched ingestion kernel')
         table[i] = (off, f.frames_read, f.frames, f.channels,
@@ -346,9 +358,12 @@ def collate_stored(files, seg_len: int = 128000, target_sr: int = 32000):
     wave = _wave_tables(files, table, seg_len, target_sr)
     extra = {}
     if wave is not None:  # a batch of 'original' draws is the plain path
-        wave_table, mono_table, mono_bytes = wave
+        wave_table, mono_table, mono_bytes, stretch_table = wave
         extra = dict(wave_off=end, mono_table_off=_align(end + wave_table.nbytes), mono_bytes=mono_bytes)
         end = _align(extra['mono_table_off'] + mono_table.nbytes)
+        if stretch_table is not None:
+            extra['stretch_off'] = end
+            end = _align(end + stretch_table.nbytes)
     buf = np.zeros(end, np.uint8)
     for row, f in zip(table, files):
         buf[row[0]:row[0] + f.samples.nbytes] = f.samples.view(np.uint8)
@@ -358,26 +373,105 @@ def collate_stored(files, seg_len: int = 128000, target_sr: int = 32000):
         buf[extra['wave_off']:extra['wave_off'] + wave_table.nbytes] = wave_table.reshape(-1).view(np.uint8)
         o = extra['mono_table_off']
         buf[o:o + mono_table.nbytes] = mono_table.reshape(-1).view(np.uint8)
+        if stretch_table is not None:
+            o = extra['stretch_off']
+            buf[o:o + stretch_table.nbytes] = stretch_table.reshape(-1).view(np.uint8)
     return StoredBatch(torch.from_numpy(buf), len(files), tiles.shape[0], table_off, tiles_off, rates,
                        torch.tensor([f.target for f in files]), torch.stack([f.aug for f in files]), seg_len, **extra)
+
+
+# ---- time and pitch: the lengths of tests/stretch_ref.py (the float64 contract)
+def pitch_rate(steps: float) -> float:
+    return 2.0 ** (-float(steps) / 12.0)
+
+
+def stretch_rates(kind: int, p0: float, p1: float):
+    """(stretch rate or None, pitch rate or None) of a kind code 6..10."""
+    k = kind - STRETCH_CODE0
+    if k in (0, 1):
+        return float(p0), None
+    if k in (2, 3):
+        return None, pitch_rate(p0)
+    return float(p0), pitch_rate(p1)
+
+
+def stretch_out_len(kind: int, frames: int, p0: float, p1: float = 0.0) -> int:
+    """The kind's output length: round(frames / rate); a pitch shift keeps its input's."""
+    rate, _ = stretch_rates(kind, p0, p1)
+    return int(frames) if rate is None else int(round(int(frames) / rate))
+
+
+def _stretch_need(rate: float, n_out: int) -> int:
+    """Output sample m sums the synthesis frames t <= (m + 1024) // 512; step t
+    reads the analysis frames int(t rate), int(t rate) + 1; frame f the samples
+    below 512 f + 1024."""
+    if n_out <= 0:
+        return 0
+    t = (n_out - 1 + STRETCH_N_FFT // 2) // STRETCH_HOP
+    return (int(t * float(rate)) + 1) * STRETCH_HOP + STRETCH_N_FFT // 2
+
+
+def _resample_need(rho: float, n_out: int) -> int:
+    if n_out <= 0:
+        return 0
+    return max(int(math.ceil((n_out - 1) / float(rho) + 6.0 / (0.99 * min(1.0, rho)))), 0)
+
+
+def stretch_need_frames(kind: int, p0: float, p1: float, n_out: int) -> int:
+    """The input frames the first n_out output frames of the kind depend on
+    (tests/stretch_ref.py need_frames): what a worker reads of the file."""
+    rate, prate = stretch_rates(kind, p0, p1)
+    n = int(n_out)
+    if prate is not None:
+        n = _stretch_need(prate, _resample_need(prate, n))
+    return n if rate is None else _stretch_need(rate, n)
+
+
+def _f64bits(v: float) -> int:
+    return int(np.array([v], np.float64).view(np.int64)[0])
 
 
 def wave_chunks(n_out: int) -> int:
     return -(-int(n_out) // WAVE_CHUNK)
 
 
+def _is_stretch(f) -> bool:
+    return f.wave is not None and f.wave[0] >= STRETCH_CODE0
+
+
+def _out_frames(f) -> int:
+    """The file's length after its waveform augmentation: a stretch changes it."""
+    return stretch_out_len(f.wave[0], f.frames, f.wave[1], f.wave[2]) if _is_stretch(f) else f.frames
+
+
 def _wave_tables(files, table, seg_len, target_sr):
     """(augmentation table [B, 8], the mono arena's file table [B, 6], the mono
-    arena's bytes) of include/sad.h "waveform augmentation", or None when every
-    file drew 'original' (kind 0) or none has a draw.  File f's output holds its
-    first min(total, need) frames: what the two segments read."""
+    arena's bytes, stretch table [B, 8] or None) of include/sad.h "waveform
+    augmentation" and "time and pitch", or None when every file drew 'original'
+    (kind 0) or none has a draw.  File f's output holds its first min(total,
+    need) frames: what the two segments read.  A file of a stretch kind (code
+    >= 6) is an empty 'original' row of the augmentation table and the other way
+    round, so the two entries fill one arena between them."""
     if all(f.wave is None or f.wave[0] == 0 for f in files):
         return None
     wave = np.zeros((len(files), WAVE_COLS), np.int64)
     mono = np.zeros((len(files), TRAIN_COLS), np.int64)
+    stretch = np.zeros((len(files), WAVE_COLS), np.int64) if any(_is_stretch(f) for f in files) else None
     off = chunks = 0
     for i, f in enumerate(files):
         kind, p0, p1, key = f.wave if f.wave is not None else (0, 0.0, 0.0, 0)
+        if kind >= STRETCH_CODE0:
+            total = _out_frames(f)
+            n_out = min(total, train_need_frames(f.sr, seg_len, target_sr))
+            rate, prate = stretch_rates(kind, p0, p1)
+            steps = p0 if rate is None else p1
+            stretch[i] = (kind, _f64bits(rate or 0.0), _f64bits(steps if prate is not None else 0.0), n_out, off,
+                          _f64bits(prate or 0.0), 0, 0)
+            wave[i, :4] = (0, f.sr, 0, off)
+            wave[i, 6] = chunks
+            mono[i] = (off, n_out, total, 1, _lib.SAD_PCM_F32, table[i, 5])
+            off = _align(off + 4 * n_out)
+            continue
         n_out = min(f.frames, f.frames_read, train_need_frames(f.sr, seg_len, target_sr))
         params = np.array([p0, p1], np.float32).view(np.uint32).astype(np.uint64)
         wave[i, :4] = (kind, f.sr, n_out, off)
@@ -387,7 +481,7 @@ def _wave_tables(files, table, seg_len, target_sr):
         mono[i] = (off, n_out, f.frames, 1, _lib.SAD_PCM_F32, table[i, 5])
         off = _align(off + 4 * n_out)
         chunks += wave_chunks(n_out)
-    return wave, mono, off
+    return wave, mono, off, stretch
 
 
 class TrainIngest:
@@ -421,6 +515,8 @@ class TrainIngest:
             src, src_bytes, table, d_table = base, batch.table_off, batch.table, base + batch.table_off
             if batch.wave_off is not None:  # stage one: augment into an fp32 mono arena, then ingest that
                 mono = self.wave_augment(batch, d_arena)
+                if batch.stretch_off is not None:  # the files of the stretch kinds, into the same arena
+                    self.wave_stretch(batch, d_arena, mono)
                 src, src_bytes, table, d_table = mono.data_ptr(), batch.mono_bytes, batch.mono_table, \
                     base + batch.mono_table_off
             _lib.call('sad_train_ingest_run', src, src_bytes, table.data_ptr(), d_table,
@@ -439,6 +535,20 @@ class TrainIngest:
         with torch.cuda.device(dev):
             _lib.call('sad_wave_augment_run', base, batch.table_off, batch.table.data_ptr(), base + batch.table_off,
                       batch.n_files, batch.wave_table.data_ptr(), base + batch.wave_off, mono.data_ptr(),
+                      batch.mono_bytes, ws.data_ptr(), need.value, _lib.stream_handle(dev))
+        return mono
+
+    def wave_stretch(self, batch: StoredBatch, d_arena: torch.Tensor, mono: torch.Tensor) -> torch.Tensor:
+        """sad_wave_stretch_run on an uploaded batch, into the arena wave_augment made
+        (file f at batch.stretch_table[f, 4], batch.stretch_table[f, 3] frames)."""
+        dev, base = self.device, d_arena.data_ptr()
+        need = _lib.SZ()
+        _lib.call('sad_wave_stretch_workspace_size', batch.table.data_ptr(), batch.stretch_table.data_ptr(),
+                  batch.n_files, ctypes.byref(need))
+        ws = torch.empty(max(need.value, 16), device=dev, dtype=torch.uint8)
+        with torch.cuda.device(dev):
+            _lib.call('sad_wave_stretch_run', base, batch.table_off, batch.table.data_ptr(), base + batch.table_off,
+                      batch.n_files, batch.stretch_table.data_ptr(), base + batch.stretch_off, mono.data_ptr(),
                       batch.mono_bytes, ws.data_ptr(), need.value, _lib.stream_handle(dev))
         return mono
 

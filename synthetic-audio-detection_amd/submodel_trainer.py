@@ -63,10 +63,18 @@ Differences (documented in DESIGN.md / INTEGRATION.md):
     dynamic_range_compression, add_white_noise, tremolo, phaser, time_shift, or
     ``all``) with parameters from the reference's ranges, and the device applies
     it to the stored samples before they are resampled (csrc/waveaug.hip,
-    sad_wave_augment_run).  The five librosa kinds (speed_up, slow_down,
-    pitch_up, pitch_down, time_pitch_shift) are refused.  Not reproduced: the
-    tool's resample to 44.1 kHz, its 16-bit file round trip, numpy's normal
-    generator; the noise's RMS runs over the frames read.
+    sad_wave_augment_run).  Not reproduced: the tool's resample to 44.1 kHz,
+    its 16-bit file round trip, numpy's normal generator; the noise's RMS runs
+    over the frames read.
+  * ``--wave-stretch LIST`` (with ``--device-ingest``, with or without
+    ``--wave-augment``; off by default): the tool's other five kinds, the ones
+    that go through librosa (speed_up, slow_down, pitch_up, pitch_down,
+    time_pitch_shift, or ``all``).  The kind is drawn from the union of both
+    lists; a phase vocoder and a resampler on the device apply it
+    (csrc/stretch.hip, sad_wave_stretch_run).  The contract is our own float64
+    restatement of librosa's documented algorithm (tests/stretch_ref.py), not
+    pinned to librosa; the pitch shift's resampler is the ingestion's windowed
+    sinc, not soxr.
   * TensorBoard is optional (not installed here): scalars are logged instead.
 """
 from __future__ import annotations
@@ -144,8 +152,15 @@ def parse_args(argv=None):
                              'and per epoch one kind is drawn uniformly from LIST, with parameters from the ranges of '
                              'the reference\'s audio_augmneter.py, and applied to the stored samples before they are '
                              f'resampled.  LIST: comma-separated names out of {", ".join(_augment.WAVE_KINDS)}, or '
-                             f'all.  Not supported: {", ".join(_augment.WAVE_UNSUPPORTED)}.  Validation and '
+                             f'all.  ({", ".join(_augment.WAVE_UNSUPPORTED)}: see --wave-stretch.)  Validation and '
                              '--evaluate are never augmented')
+    parser.add_argument('--wave-stretch', default='', type=str, metavar='LIST',
+                        help='time-stretch and pitch-shift augmentation of the train split on the device (needs '
+                             '--device-ingest; works with or without --wave-augment): the kind of a file is drawn '
+                             'uniformly from the union of both lists, its rate / semitone steps from the ranges of the '
+                             f'reference\'s audio_augmneter.py.  LIST: comma-separated names out of '
+                             f'{", ".join(_augment.STRETCH_KINDS)}, or all.  Validation and --evaluate are never '
+                             'augmented')
     args = parser.parse_args(argv)
     if args.wave_augment:
         if not args.device_ingest:
@@ -157,6 +172,16 @@ def parse_args(argv=None):
             parser.error(f'--wave-augment: {e}')
     else:
         args.wave_augment = None
+    if args.wave_stretch:
+        if not args.device_ingest:
+            parser.error('--wave-stretch needs --device-ingest: the stretch runs on the stored samples that the '
+                         'device ingestion uploads')
+        try:
+            args.wave_stretch = _augment.parse_stretch_kinds(args.wave_stretch)
+        except ValueError as e:
+            parser.error(f'--wave-stretch: {e}')
+    else:
+        args.wave_stretch = None
     if args.trunk:
         if args.model_name != 'resnet18':
             parser.error(f'--trunk needs --model-name resnet18 (got {args.model_name}): the frozen trunk runs on '
@@ -279,8 +304,23 @@ class StoredSampleDataset(SpectrogramDataset):
     differs): a tuple of names out of ``sad.augment.WAVE_KINDS``.  Per visit one
     kind and its parameters are drawn AFTER the SpecAugment and crop draws, so
     those read the same as without the flag; with ``time_shift`` in the list the
-    worker reads half a second more, the samples a left shift brings in."""
+    worker reads half a second more, the samples a left shift brings in.
+
+    ``stretch_kinds`` (``--wave-stretch``; None = off, and then nothing differs):
+    a tuple out of ``sad.augment.STRETCH_KINDS``.  The one kind of a visit is then
+    drawn from the union of both tuples, still after the SpecAugment and crop
+    draws but BEFORE the read, because a stretch decides how much of the file the
+    two segments depend on (``sad.ingest.stretch_need_frames``).  Without the flag
+    the draws stay where they were, after the read: a file whose read fails has
+    always been dropped without consuming a draw, and moving the draws would
+    change the sequence of every later file of that worker.  The segment rule
+    (two / first / pad / drop) that decides whether the file is kept is applied to
+    the file's own length, before the draw; the device then cuts the segments
+    from the stretched length.  A file that speed_up brings below 0.9 segments is
+    therefore kept and zero-padded, where a tree written ahead of time by the
+    reference's tool would hold a variant that the trainer drops."""
     wave_kinds = None
+    stretch_kinds = None
 
     def __getitem__(self, index):
         from sad import ingest as _ingest
@@ -300,13 +340,20 @@ class StoredSampleDataset(SpectrogramDataset):
                               f"Required: {2 * SEGMENT_LENGTH}")
                 return None
             need = _ingest.train_need_frames(sample_rate, SEGMENT_LENGTH, 32000)
-            if self.wave_kinds and 'time_shift' in self.wave_kinds:
+            aug = wave = None
+            if self.stretch_kinds:  # the draw sets how much is read; without the flag: after the read, as ever
+                aug = self._aug_params()
+                wave = _augment.wave_stretch_params(self.wave_kinds, self.stretch_kinds, sample_rate)
+            if wave is not None and wave[0] >= _ingest.STRETCH_CODE0:
+                need = _ingest.stretch_need_frames(wave[0], wave[1], wave[2], need)
+            elif self.wave_kinds and 'time_shift' in self.wave_kinds:
                 need += int(_augment.WAVE_SHIFT_MARGIN * sample_rate)
             samples, _, _ = _audio.read_wav(path, max_frames=min(frames, need))
             if samples.shape[0] != min(frames, need) * channels:
                 raise ValueError('the data chunk is shorter than its header says')
-            aug = self._aug_params()
-            wave = _augment.wave_aug_params(self.wave_kinds, sample_rate) if self.wave_kinds else None
+            if not self.stretch_kinds:
+                aug = self._aug_params()
+                wave = _augment.wave_aug_params(self.wave_kinds, sample_rate) if self.wave_kinds else None
             return _ingest.StoredFile(samples, frames, channels, sample_rate, target, aug, wave)
         except Exception as e:
             logging.warning(f"Error processing file at index {index}, path {path}: {str(e)}")
@@ -542,6 +589,8 @@ def get_dataloaders(args, rank: int = 0, world: int = 1):
     val_dataset = dataset_cls(args.data_dir, 'test', transform='val', class_names=[args.Class0, args.Class1])
     if stored and getattr(args, 'wave_augment', None):  # the train split only
         train_dataset.wave_kinds = tuple(args.wave_augment)
+    if stored and getattr(args, 'wave_stretch', None):  # the train split only
+        train_dataset.stretch_kinds = tuple(args.wave_stretch)
     per_rank = args.batch_size if world > 1 else (args.batch_size * args.num_gpus if args.num_gpus > 0
                                                    else args.batch_size)
     logging.info(f"Total batch size: {per_rank * world}")
